@@ -12,7 +12,17 @@ value = ndofs_global * K / (1e9 * t), t = MAX over ranks of the K-step time
 (barrier + device sync on both sides).  Weak scaling: --dofs-per-gpu fixed.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config q3|q6|q6f32]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: set up,
+warm up, time the K steps, write the outputs if --dump-outputs is given, print
+the result line.  Everything else the benchmark measures or checks (the
+operator-action check and the cross-family consistency gate, the Q6 / FP32 /
+random-coefficient companions, the one-rank variants in child processes, the
+N > 1 data-model record, the hipEvent phase profile, the box's stream / DGEMM
+probe) runs with --full only, where --companions / --extras / --box-probe /
+--profile-steps select among them as before.
 
 `python bench.py --gpus N` (N > 1, no torchrun environment) launches the N
 ranks itself: this parent process starts N children with RANK / LOCAL_RANK /
@@ -64,23 +74,46 @@ def parse_args(argv=None):
     ap.add_argument("--mesh", default=None,
                     help="experiments only: explicit global cell counts NX,NY,NZ instead of "
                          "the config's DoF target")
-    ap.add_argument("--profile-steps", type=int, default=5,
-                    help="extra eager iterations with hipEvent phase timers (0: none)")
-    ap.add_argument("--companions", default="auto", choices=["auto", "on", "off"],
-                    help="after the Q3 headline, time the metric's second half (Q6 at 500 M "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the operator-action "
+                         "check and the consistency gate, the companions, the variants, the "
+                         "phase profile and the box probe (see the options below; without "
+                         "--full they are all off)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed (the CG iterate x of "
+                         "the last step and its norm) as DIR/<name>.npy (float64; a fixed seeded "
+                         "sample of x when it is large)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="--full: extra eager iterations with hipEvent phase timers (default 5; "
+                         "0: none)")
+    ap.add_argument("--companions", default=None, choices=["auto", "on", "off"],
+                    help="--full: after the Q3 headline, time the metric's second half (Q6 at 500 M "
                          "DoFs/GPU, FP64 and FP32) and the headline with per-cell random "
                          "coefficients, each with the same steps/warmup, and report q6_gdofs / "
-                         "q6f32_gdofs / random_kappa_gdofs (auto: on for the q3 config)")
-    ap.add_argument("--extras", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline, time variants of it: the perturbed "
+                         "q6f32_gdofs / random_kappa_gdofs (default auto: on for the q3 config)")
+    ap.add_argument("--extras", default=None, choices=["auto", "on", "off"],
+                    help="--full: after the headline, time variants of it: the perturbed "
                          "(general trilinear) mesh, the "
                          "reference's data model (dofmap + stored G, Q3 and Q6, on its VALU "
                          "and its MFMA kernel), Q6 perturbed and Q6 FP32 perturbed (FP32 "
-                         "MFMA) (GPU only; auto: on for one rank)")
-    ap.add_argument("--box-probe", default="on", choices=["on", "off"],
-                    help="after every timed run, measure the box's HBM stream rate "
-                         "(untimed context: config.box_stream)")
-    return ap.parse_args(argv)
+                         "MFMA) (GPU only; default auto: on for one rank)")
+    ap.add_argument("--box-probe", default=None, choices=["on", "off"],
+                    help="--full: after every timed run, measure the box's HBM stream rate "
+                         "(untimed context: config.box_stream; default on)")
+    a = ap.parse_args(argv)
+    # the secondary measurements exist under --full only: there the options
+    # above default to what they always did, without it they are off and a
+    # request for one of them is an error rather than silently dropped
+    for name, full_default, off in (("companions", "auto", "off"), ("extras", "auto", "off"),
+                                    ("box_probe", "on", "off"), ("profile_steps", 5, 0)):
+        v = getattr(a, name)
+        if a.full:
+            setattr(a, name, full_default if v is None else v)
+        elif v not in (None, off):
+            ap.error(f"--{name.replace('_', '-')} {v} needs --full")
+        else:
+            setattr(a, name, off)
+    return a
 
 
 def _median(v):
@@ -97,10 +130,12 @@ def _pair_means(v):
 
 
 def _measure(comm, a, config, steps, warmup, *, kappa="constant", perturb=0.0,
-             kernel="auto", geometry="auto", profile_steps=0, log=None) -> dict:
+             kernel="auto", geometry="auto", profile_steps=0, log=None,
+             dump_dir=None) -> dict:
     """Build one config, run `warmup` untimed and `steps` timed CG
     iterations (barrier + device sync on both sides, MAX over ranks) and
-    return its record (identical on every rank)."""
+    return its record (identical on every rank).  `dump_dir`: write the
+    outputs of the timed steps there (`_dump_outputs`)."""
     import torch
 
     from benchmark_dolfinx_amd.driver import make_operator
@@ -136,9 +171,9 @@ def _measure(comm, a, config, steps, warmup, *, kappa="constant", perturb=0.0,
     mark("rhs")
     op = make_operator(pb, kernel, geometry)
     mark("operator")
-    # one operator action on the RHS before the CG (untimed): the
+    # --full: one operator action on the RHS before the CG (untimed): the
     # cross-family consistency check of _record compares these scalars
-    check = _action_check(pb, op, u)
+    check = _action_check(pb, op, u) if getattr(a, "full", False) else None
 
     def sync():
         if gpu:
@@ -190,6 +225,8 @@ def _measure(comm, a, config, steps, warmup, *, kappa="constant", perturb=0.0,
             f.write(json.dumps({"config": config, "kernel": kernel, "perturb": perturb,
                                 "step_ms": step_ms}) + "\n")
     ynorm = pb.norm(x)
+    if dump_dir:
+        _dump_outputs(dump_dir, comm, pb, x, ynorm)
     rt = getattr(op, "_rt", None)
     rec = {
         "value": value,
@@ -260,6 +297,39 @@ def _measure(comm, a, config, steps, warmup, *, kappa="constant", perturb=0.0,
     if gpu:
         torch.cuda.empty_cache()
     return rec
+
+
+DUMP_FULL_MAX = 1 << 22   # owned values of x up to which all of them are written
+DUMP_SAMPLE = 1 << 21     # size of the sample of a larger x
+DUMP_SEED = 20240229
+
+
+def _dump_outputs(dump_dir, comm, pb, x, ynorm) -> None:
+    """--dump-outputs: what a caller of the timed path receives after its last
+    step, as float64 .npy files: `x` (the CG iterate over this rank's owned
+    dofs in lattice order, z fastest) and `y_norm` (its global l2 norm).  An x
+    of more than DUMP_FULL_MAX values is written as DUMP_SAMPLE of them, at
+    sorted positions of the flattened owned lattice drawn once from
+    numpy's default_rng(DUMP_SEED): the same positions in every run with the
+    same arguments (at most 32 MB either way).  With several ranks each
+    writes its own block as x_rank<r>.npy."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    xo = pb.owned(x)
+    n = xo.numel()
+    if n <= DUMP_FULL_MAX:
+        out = xo.detach().double().cpu().numpy()
+    else:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE))
+        i, j, k = np.unravel_index(pos, tuple(xo.shape))
+        i, j, k = (torch.from_numpy(v).to(xo.device) for v in (i, j, k))
+        out = xo[i, j, k].detach().double().cpu().numpy()
+    name = "x" if comm.size == 1 else f"x_rank{comm.rank}"
+    np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(out, dtype=np.float64))
+    if comm.rank == 0:
+        np.save(os.path.join(dump_dir, "y_norm.npy"), np.array([ynorm], dtype=np.float64))
 
 
 def _emulated_prediction(config: str, kernel: str, n: int):
@@ -360,15 +430,16 @@ def _measure_env(comm, a, config, steps, warmup, *, extra_env=None, **kw) -> dic
 
 def _measure_isolated(a, config, steps, warmup, *, kappa="constant", perturb=0.0,
                       kernel="auto", geometry="auto", extra_env=None, log=None) -> dict:
-    """One-rank `_measure` in a child interpreter (this script, headline only,
-    no companions / variants; `extra_env`: added to the child's environment); returns
-    the child's record with its own clock.  The parent has released its
-    cached device memory, and never execs: the child is a fresh process
-    started with Popen semantics."""
+    """One-rank `_measure` in a child interpreter (this script, headline and
+    its action check only: --full with no companions / variants / probes;
+    `extra_env`: added to the child's environment); returns the child's
+    record with its own clock.  The parent has released its cached device
+    memory, and never execs: the child is a fresh process started with Popen
+    semantics."""
     import subprocess
 
     argv = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--config", config,
-            "--steps", str(steps), "--warmup", str(warmup), "--companions", "off",
+            "--steps", str(steps), "--warmup", str(warmup), "--full", "--companions", "off",
             "--extras", "off", "--box-probe", "off", "--profile-steps", "0", "--kappa", kappa,
             "--perturb", repr(float(perturb)), "--kernel", kernel, "--geometry", geometry,
             "--platform", a.platform]
@@ -462,7 +533,7 @@ def run(comm, a) -> dict | None:
 
     head = _measure(comm, a, a.config, a.steps, a.warmup, kappa=a.kappa, perturb=a.perturb,
                     kernel=a.kernel, geometry=a.geometry, profile_steps=a.profile_steps,
-                    log=log)
+                    log=log, dump_dir=a.dump_outputs)
     # the metric's second half (Q6 at 500 M DoFs/GPU, FP64 and FP32) and the
     # north star's random coefficients on the headline config, each on the
     # headline's clock discipline (own steps / warmup / ms_per_step), at

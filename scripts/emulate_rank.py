@@ -67,7 +67,7 @@ def main(argv=None) -> int:
 
     from benchmark_dolfinx_amd.parallel.comm import Comm, EmulatedRankComm
     torch.cuda.set_device(0)
-    ba = bench.parse_args(["--config", a.config])
+    ba = bench.parse_args(["--config", a.config, "--full"])
     link = {k: float(os.environ.get(k, d)) for k, d in (("BDX_EMU_LINK_GBPS", 50.0),
                                                         ("BDX_EMU_LINK_LAT_US", 10.0),
                                                         ("BDX_EMU_ALLREDUCE_US", 20.0))}
@@ -101,7 +101,8 @@ def main(argv=None) -> int:
            "margin_ms": (ph["t_op_interior_done"] - ph["t_halo_rev_done"]) if ph else None}
     print(json.dumps(out), flush=True)
     if not a.no_single:
-        ba1 = bench.parse_args(["--config", a.config, "--mesh", ",".join(map(str, block))])
+        ba1 = bench.parse_args(["--config", a.config, "--full", "--mesh",
+                                ",".join(map(str, block))])
         r1 = bench._measure(Comm(), ba1, a.config, a.steps, a.warmup,
                             profile_steps=a.profile_steps, kernel=a.kernel,
                             geometry=a.geometry, log=log)

@@ -36,7 +36,7 @@ def main():
     def job(comm, dpg):
         args = bench.parse_args(["--config", a.config, "--dofs-per-gpu", str(dpg), "--steps",
                                  str(a.steps), "--warmup", "2", "--gpus", str(comm.size),
-                                 "--companions", "off", "--extras", "off"])
+                                 "--full", "--companions", "off", "--extras", "off"])
         out = bench.run(comm, args)
         torch.cuda.synchronize()
         return out

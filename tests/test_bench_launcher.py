@@ -36,7 +36,7 @@ def _line(r):
 
 
 def test_self_launch_four_ranks_matches_one_rank():
-    common = ["--steps", "3", "--warmup", "1", "--profile-steps", "0"]
+    common = ["--steps", "3", "--warmup", "1", "--full", "--profile-steps", "0"]
     one = _line(_bench(["--gpus", "1", "--dofs-per-gpu", "24000", *common]))
     four = _line(_bench(["--gpus", "4", "--dofs-per-gpu", "6000", *common]))
     # the metric's Q6 half rides along (own steps / ms_per_step), FP64 and
@@ -106,7 +106,7 @@ def test_failed_companion_on_several_ranks_reports_headline_and_error():
     that skipped ahead would pair up the wrong collectives), but rank 0 still
     prints one JSON line: the headline it measured and the error."""
     r = _bench(["--gpus", "2", "--dofs-per-gpu", "6000", "--steps", "2", "--warmup", "1",
-                "--profile-steps", "0"], timeout=300, BDX_BENCH_FAIL_MEASURE="q6f32")
+                "--full", "--profile-steps", "0"], timeout=300, BDX_BENCH_FAIL_MEASURE="q6f32")
     assert r.returncode != 0
     lines = [s for s in r.stdout.splitlines() if s.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -131,11 +131,12 @@ def test_multirank_run_records_the_reference_data_model():
     with the C++ CPU dofmap operator (the GPU path is the same code with the
     HIP kernel and RCCL, tests/test_gpu_distributed_emulated.py)."""
     one = _line(_bench(["--gpus", "1", "--dofs-per-gpu", "24000", "--steps", "3", "--warmup",
-                        "1", "--profile-steps", "0", "--companions", "off"]))
+                        "1", "--full", "--profile-steps", "0", "--companions", "off"]))
     assert not one["variants"]  # one CPU rank: no variants (GPU-only extras)
     for n in (2, 4, 8):
         rec = _line(_bench(["--gpus", str(n), "--dofs-per-gpu", str(24000 // n), "--steps", "3",
-                            "--warmup", "1", "--profile-steps", "0", "--companions", "off"],
+                            "--warmup", "1", "--full", "--profile-steps", "0", "--companions",
+                            "off"],
                            timeout=400, BDX_PARTITION="yz"))
         dm = rec["variants"]["dofmap"]
         assert dm.get("error") is None, dm

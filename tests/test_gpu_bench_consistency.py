@@ -24,7 +24,7 @@ def _bench(**env):
         e.pop(k, None)
     e.update(env)
     args = [sys.executable, "bench.py", "--dofs-per-gpu", "2000000", "--steps", "3", "--warmup",
-            "1", "--companions", "off", "--extras", "on", "--box-probe", "off",
+            "1", "--full", "--companions", "off", "--extras", "on", "--box-probe", "off",
             "--profile-steps", "0"]
     return subprocess.run(args, cwd=ROOT, env=e, capture_output=True, text=True, timeout=420)
 

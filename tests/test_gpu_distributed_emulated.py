@@ -20,7 +20,7 @@ def _bench(comm, config, total, kernel="auto", geometry="auto"):
     import bench
     a = bench.parse_args(["--config", config, "--dofs-per-gpu", str(total // comm.size),
                           "--steps", "6", "--warmup", "2", "--kernel", kernel,
-                          "--geometry", geometry, "--gpus", str(comm.size)])
+                          "--geometry", geometry, "--gpus", str(comm.size), "--full"])
     out = bench.run(comm, a)
     torch.cuda.synchronize()
     return out

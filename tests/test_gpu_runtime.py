@@ -237,7 +237,7 @@ def test_bench_entry_point_one_gpu():
     env = dict(os.environ)
     env["PYTHONPATH"] = ROOT + os.pathsep + env.get("PYTHONPATH", "")
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dofs-per-gpu", "2000000",
-                        "--steps", "5", "--warmup", "2"], cwd=ROOT, env=env,
+                        "--steps", "5", "--warmup", "2", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
