@@ -56,7 +56,10 @@ def declare(lib) -> None:
         _d(lib, f"bdx_fused_finalize_{suf}", [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp])
         _d(lib, f"bdx_cg_update_iface_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
                                                 vp, i32, i32, i32, vp, vp])
+        _d(lib, f"bdx_cg_update_tiled_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                                vp, i32, i32, i32, vp, vp])
         _d(lib, f"bdx_xflush_{suf}", [vp, vp, vp, vp, vp, i32, i32, vp])
+        _d(lib, f"bdx_flush_export_{suf}", [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp])
         _d(lib, f"bdx_fused_tables_{suf}", [i32, i32, vp, vp, vp])
         _d(lib, f"bdx_fused3_tables_{suf}", [i32, i32, vp, vp, vp])
         for P in range(1, 8):

@@ -214,6 +214,43 @@ def test_random_coefficients_vs_oracle(nc, P, qm, pert):
     assert np.abs(pb.to_global_array(z) - yr).max() <= 1e-11 * np.abs(yr).max()
 
 
+@pytest.mark.parametrize("nc,P,qm,pert,kappa", [((3, 2, 4), 3, 1, 0.2, "const"),
+                                                ((2, 3, 2), 4, 0, 0.15, "random"),
+                                                ((2, 2, 3), 2, 1, 0.25, "random")])
+def test_stored_geometry_path_matches_on_the_fly(nc, P, qm, pert, kappa, monkeypatch):
+    """The CPU operator with the geometry factors precomputed per cell
+    (BDX_CPU_G_MAX_BYTES; off by default, so no other test enters it) against
+    the default, which evaluates them per quadrature point.
+
+    Tolerance: both paths evaluate the same formula for G (about 50
+    operations per entry); they can differ only in how the compiler orders or
+    contracts them, i.e. by at most ~100 unit roundoffs relative to an entry
+    (the minors of the Jacobian cancel by a small factor on a mesh perturbed
+    by a quarter of a cell at most).  y is linear in G, and the magnitudes of
+    the signed products behind one y_i sum to roughly 10 max|y| for a random
+    u: |dy| <= 100 * 1.1e-16 * 10 max|y| ~ 1e-13 max|y|.  An error in the
+    stored layout or in the cell indexing changes y by O(max|y|)."""
+    args = (Comm(), nc, P, qm, False, torch.float64, "cpu", pert)
+    pb = PoissonProblem(*args, "random") if kappa == "random" else PoissonProblem(*args)
+    rng = np.random.default_rng(5)
+    u = pb.new_vector()
+    u[:, :, : pb.lat.L[2]] = torch.from_numpy(rng.standard_normal(pb.lat.L))
+    monkeypatch.delenv("BDX_CPU_G_MAX_BYTES", raising=False)
+    otf = MatFreeLaplacianCPU(pb)
+    assert otf.G is None
+    monkeypatch.setenv("BDX_CPU_G_MAX_BYTES", str(1 << 30))
+    stored = MatFreeLaplacianCPU(pb)
+    nq = pb.tables.nq
+    assert stored.G is not None and stored.G.size == int(np.prod(nc)) * 6 * nq ** 3
+    assert np.isfinite(stored.G).all()
+    y_otf, y_st = pb.new_vector(), pb.new_vector()
+    otf.apply(u, y_otf)
+    stored.apply(u, y_st)
+    scale = y_otf.abs().max().item()
+    assert scale > 1.0
+    assert (y_st - y_otf).abs().max().item() <= 1e-13 * scale
+
+
 @pytest.mark.parametrize("R", [2, 4])
 def test_random_coefficients_partition_invariant(R):
     def body(comm):
