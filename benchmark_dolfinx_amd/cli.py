@@ -11,7 +11,8 @@ Reference options (src/main.cpp:144-183): --platform, --float, --ndofs,
 
 MI355X extensions (additive): --kernel {auto,fused5,fused3,fused2,
 fused,v1,dofmap}, --geometry {auto,otf,otf-general,stored}, --kappa {constant,random},
---warmup N (untimed repetitions before the timed loop).
+--warmup N (untimed repetitions before the timed loop), --precond {none,jacobi}
+(with --cg: Jacobi-preconditioned CG with the matrix-free operator diagonal).
 The JSON gains an additive "mi355x" object; the reference keys are
 unchanged.
 """
@@ -68,6 +69,9 @@ def build_parser() -> argparse.ArgumentParser:
                          "per-cell field U(1, 3) (partition-invariant)")
     ap.add_argument("--warmup", type=int, default=0,
                     help="Untimed repetitions before the timed loop")
+    ap.add_argument("--precond", default="none", choices=["none", "jacobi"],
+                    help="CG preconditioner (needs --cg): jacobi = the inverse of the "
+                         "matrix-free operator diagonal")
     return ap
 
 
@@ -80,6 +84,8 @@ def parse_args(argv=None):
         raise SystemExit("error: Invalid float size. Must be 32 or 64.")
     if args.qmode > 1 or args.qmode < 0:
         raise SystemExit("error: Invalid qmode.")
+    if args.precond != "none" and not args.cg:
+        raise SystemExit("error: Option 'precond' needs 'cg'")
     return args, unknown
 
 
@@ -123,6 +129,8 @@ def main(argv=None) -> int:
         print(f"Scalar Type: {args.float}")
         print(f"Use Gauss-Jacobi: {int(args.use_gauss)}")
         print(f"Compare to matrix: {int(args.mat_comp)}")
+        if args.precond != "none":
+            print(f"Preconditioner: {args.precond}")
         print("-----------------------------------", flush=True)
 
     in_root = {"p": args.degree, "mpi_size": size, "ndofs_local_requested": ndofs,
@@ -168,7 +176,7 @@ def run_benchmark(comm, nx, args, platform):
     pb = PoissonProblem(comm, nx, args.degree, args.qmode, args.use_gauss, dtype,
                         platform, args.geom_perturb_fact, args.kappa)
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
-                         geometry=args.geometry, warmup=args.warmup)
+                         geometry=args.geometry, warmup=args.warmup, precond=args.precond)
     t = res.mat_free_time
     gdofs = pb.ndofs_global * args.nreps / (1e9 * t) if t > 0 else 0.0
     out = {"ncells_global": pb.ncells_global, "ndofs_global": pb.ndofs_global,

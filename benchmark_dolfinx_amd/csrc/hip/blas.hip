@@ -99,6 +99,58 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// Jacobi-preconditioned CG (z = dinv . r is never stored):
+// alpha = s[rz] / s[pap];  x += alpha p;  r -= alpha y;  per-block partials of
+// r.z = sum dinv r^2 (partials[0 .. grid)) and r.r (partials[grid .. 2 grid)).
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+    pcg_update_kernel(RowSpace s, T* __restrict__ x, T* __restrict__ r,
+                      const T* __restrict__ p, const T* __restrict__ y,
+                      const T* __restrict__ dinv, const double* __restrict__ scal, int rz_slot,
+                      int pap_slot, double* __restrict__ partials) {
+  __shared__ double lds_rz[16], lds_rr[16];
+  const T alpha = static_cast<T>(scal[rz_slot] / scal[pap_slot]);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t nrows = s.o0 * s.o1;
+  double acc_rz = 0.0, acc_rr = 0.0;
+  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
+       row += static_cast<int64_t>(gridDim.x) * kWaves) {
+    const int64_t base = row_base(s, row);
+    for (int64_t k = lane; k < s.o2; k += 64) {
+      const int64_t i = base + k;
+      x[i] = x[i] + alpha * p[i];
+      const T rn = r[i] - alpha * y[i];
+      r[i] = rn;
+      const double rr = static_cast<double>(rn) * static_cast<double>(rn);
+      acc_rr += rr;
+      acc_rz += static_cast<double>(dinv[i]) * rr;
+    }
+  }
+  const double tz = block_sum(acc_rz, lds_rz);
+  const double tr = block_sum(acc_rr, lds_rr);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = tz;
+    partials[gridDim.x + blockIdx.x] = tr;
+  }
+}
+
+// p = beta p + dinv . r with beta = s[num] / s[den] (owned rows).
+template <typename T>
+__global__ void __launch_bounds__(kBlock)
+    pcg_p_update_kernel(RowSpace s, T* __restrict__ p, const T* __restrict__ r,
+                        const T* __restrict__ dinv, const double* __restrict__ scal, int num,
+                        int den) {
+  const T beta = static_cast<T>(scal[num] / scal[den]);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t nrows = s.o0 * s.o1;
+  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
+       row += static_cast<int64_t>(gridDim.x) * kWaves) {
+    const int64_t base = row_base(s, row);
+    for (int64_t k = lane; k < s.o2; k += 64)
+      p[base + k] = beta * p[base + k] + dinv[base + k] * r[base + k];
+  }
+}
+
 // out = alpha x + y over owned rows (reference axpy, src/vector.hpp:228-240).
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -312,6 +364,30 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
     p_update_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(s, p, r,    \
                                                                   scal, num,  \
                                                                   den);       \
+    return static_cast<int>(hipGetLastError());                               \
+  }                                                                           \
+  /* Jacobi PCG update: r.z -> scal[out_slot], r.r -> scal[rr_slot] */        \
+  int bdx_pcg_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,    \
+                           int64_t o2, T* x, T* r, const T* p, const T* y,    \
+                           const T* dinv, double* scal, int rz_slot,          \
+                           int pap_slot, int out_slot, int rr_slot,           \
+                           double* partials, hipStream_t st) {                \
+    RowSpace s{L1, ld, o0, o1, o2};                                           \
+    const int g = grid_for_rows(o0 * o1);                                     \
+    pcg_update_kernel<T><<<g, kBlock, 0, st>>>(s, x, r, p, y, dinv, scal,     \
+                                               rz_slot, pap_slot, partials);  \
+    reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials, g, scal, out_slot); \
+    reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials + g, g, scal,       \
+                                                 rr_slot);                    \
+    return static_cast<int>(hipGetLastError());                               \
+  }                                                                           \
+  int bdx_pcg_p_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,  \
+                             int64_t o2, T* p, const T* r, const T* dinv,     \
+                             const double* scal, int num, int den,            \
+                             hipStream_t st) {                                \
+    RowSpace s{L1, ld, o0, o1, o2};                                           \
+    pcg_p_update_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(        \
+        s, p, r, dinv, scal, num, den);                                       \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
   int bdx_axpy_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,          \

@@ -597,6 +597,102 @@ struct Mass {
   };
 };
 
+// d += diag(A_cell) for one cell, matrix-free (host twin of lap_diag.h): with
+// B = phi0, Dd = dphi1 phi0 and the pointwise products BB, DD, BD the sum
+//   kappa sum_q [G0 DDx BBy BBz + G3 BBx DDy BBz + G5 BBx BBy DDz
+//                + 2 G1 BDx BDy BBz + 2 G2 BDx BBy BDz + 2 G4 BBx BDy BDz]
+// is contracted along z, y, x (6 -> 6 -> 3 -> 1 arrays).  Dirichlet dofs are
+// skipped; the caller sets them to 1.
+template <typename T, int ND, int NQ>
+void diag_cell(const BdxLattice& lat, const T* Bt, const T* Dt, const T* wts, const T* qpts,
+               const T* xv, T kappa, const T* kc, T* d, int64_t cx, int64_t cy, int64_t cz) {
+  if (kc) kappa = kc[(cx * lat.n[1] + cy) * lat.n[2] + cz];
+  T BB[NQ][ND], DD[NQ][ND], BD[NQ][ND];
+  for (int q = 0; q < NQ; ++q)
+    for (int i = 0; i < ND; ++i) {
+      const T b = Bt[q * ND + i], dd = Dt[q * ND + i];
+      BB[q][i] = b * b;
+      DD[q][i] = dd * dd;
+      BD[q][i] = b * dd;
+    }
+  T X[8][3];
+  cell_vertices(lat, xv, cx, cy, cz, X);
+  // z stage
+  T a[6][NQ][NQ][ND];
+  for (int qx = 0; qx < NQ; ++qx)
+    for (int qy = 0; qy < NQ; ++qy) {
+      T G[NQ][6];
+      for (int qz = 0; qz < NQ; ++qz) {
+        geometry_point<T>(X, qpts[qx], qpts[qy], qpts[qz], wts[qx] * wts[qy] * wts[qz], G[qz]);
+        for (int c = 0; c < 6; ++c) G[qz][c] *= kappa;
+      }
+      for (int k = 0; k < ND; ++k) {
+        T s[6] = {0, 0, 0, 0, 0, 0};
+        for (int qz = 0; qz < NQ; ++qz) {
+          s[0] += G[qz][0] * BB[qz][k];
+          s[1] += G[qz][3] * BB[qz][k];
+          s[2] += G[qz][5] * DD[qz][k];
+          s[3] += G[qz][1] * BB[qz][k];
+          s[4] += G[qz][2] * BD[qz][k];
+          s[5] += G[qz][4] * BD[qz][k];
+        }
+        for (int c = 0; c < 3; ++c) a[c][qx][qy][k] = s[c];
+        for (int c = 3; c < 6; ++c) a[c][qx][qy][k] = 2 * s[c];
+      }
+    }
+  // y stage
+  T cDD[NQ][ND][ND], cBB[NQ][ND][ND], cBD[NQ][ND][ND];
+  for (int qx = 0; qx < NQ; ++qx)
+    for (int j = 0; j < ND; ++j)
+      for (int k = 0; k < ND; ++k) {
+        T s0 = 0, s1 = 0, s2 = 0;
+        for (int qy = 0; qy < NQ; ++qy) {
+          s0 += a[0][qx][qy][k] * BB[qy][j];
+          s1 += a[1][qx][qy][k] * DD[qy][j] + a[2][qx][qy][k] * BB[qy][j] +
+                a[5][qx][qy][k] * BD[qy][j];
+          s2 += a[3][qx][qy][k] * BD[qy][j] + a[4][qx][qy][k] * BB[qy][j];
+        }
+        cDD[qx][j][k] = s0;
+        cBB[qx][j][k] = s1;
+        cBD[qx][j][k] = s2;
+      }
+  // x stage and scatter
+  const int64_t P = lat.P;
+  for (int i = 0; i < ND; ++i)
+    for (int j = 0; j < ND; ++j)
+      for (int k = 0; k < ND; ++k) {
+        const int64_t li = cx * P + i, lj = cy * P + j, lk = cz * P + k;
+        if (lat.is_bc(li, lj, lk)) continue;
+        T s = 0;
+        for (int qx = 0; qx < NQ; ++qx)
+          s += cDD[qx][j][k] * DD[qx][i] + cBB[qx][j][k] * BB[qx][i] + cBD[qx][j][k] * BD[qx][i];
+        d[lat.idx(li, lj, lk)] += s;
+      }
+}
+
+template <typename T>
+struct DiagArgs {
+  BdxLattice lat;
+  const T *B, *Dd, *wts, *qpts, *xv;
+  T kappa;
+  const T* kc;
+  T* d;
+  int64_t lo[3], hi[3];
+};
+
+template <typename T>
+struct Diag {
+  template <int ND, int NQ>
+  struct K {
+    static void run(const DiagArgs<T>& a) {
+      for_cells(a.lo, a.hi, [&](int64_t cx, int64_t cy, int64_t cz) {
+        diag_cell<T, ND, NQ>(a.lat, a.B, a.Dd, a.wts, a.qpts, a.xv, a.kappa, a.kc, a.d, cx, cy,
+                             cz);
+      });
+    }
+  };
+};
+
 template <typename T>
 Tables<T> make_tables(const T* phi0, const T* dphi1, const T* wts,
                       const T* qpts, const T* nodes, int identity) {
@@ -824,6 +920,28 @@ int bdx_host_version() { return 1; }
       a.hi[d] = hi[d];                                                        \
     }                                                                         \
     dispatch<Mass<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
+  }                                                                           \
+  /* d += matrix-free diag(A) of the cells [lo, hi) (B = phi0, Dd = dphi1 */ \
+  /* phi0; Dirichlet dofs skipped): the host twin of bdx_diag */              \
+  void bdx_cpu_diag_##SUF(const int64_t* latd, int nq, const T* B,            \
+                          const T* Dd, const T* wts, const T* qpts,           \
+                          const T* xv, T kappa, const T* kc, T* d,            \
+                          const int64_t* lo, const int64_t* hi) {             \
+    DiagArgs<T> a;                                                            \
+    a.lat = BdxLattice::from(latd);                                           \
+    a.B = B;                                                                  \
+    a.Dd = Dd;                                                                \
+    a.wts = wts;                                                              \
+    a.qpts = qpts;                                                            \
+    a.xv = xv;                                                                \
+    a.kappa = kappa;                                                          \
+    a.kc = kc;                                                                \
+    a.d = d;                                                                  \
+    for (int c = 0; c < 3; ++c) {                                             \
+      a.lo[c] = lo[c];                                                        \
+      a.hi[c] = hi[c];                                                        \
+    }                                                                         \
+    dispatch<Diag<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
   }                                                                           \
   int64_t bdx_cpu_csr_##SUF(const int64_t* latd, int nq, const T* B,          \
                             const T* Dd, const T* wts, const T* qpts,         \

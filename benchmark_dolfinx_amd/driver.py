@@ -109,13 +109,13 @@ def _sync(pb: PoissonProblem) -> None:
         torch.cuda.synchronize()
 
 
-def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg):
+def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg, dinv=None):
     if use_cg:
         if pb.platform == "gpu":
             dev_cg.solve(op, x, u, nreps)
             dev_cg.wait()  # bounded by the RCCL deadline (native runtime)
         else:
-            cg_solve(op, pb, x, u, nreps, 0.0)
+            cg_solve(op, pb, x, u, nreps, 0.0, dinv=dinv)
     else:
         for _ in range(nreps):
             op.apply(u, x)
@@ -123,7 +123,16 @@ def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg):
 
 def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
                    kernel: str = "auto", geometry: str = "auto", warmup: int = 0,
-                   printer=print) -> BenchmarkResults:
+                   printer=print, precond: str = "none") -> BenchmarkResults:
+    """precond="jacobi" (CG only): Jacobi-preconditioned CG with the
+    matrix-free diagonal; the CSR comparison solve is then preconditioned
+    with the diagonal read off the assembled matrix, so the error norm
+    cross-checks the two diagonals end to end."""
+    if precond not in ("none", "jacobi"):
+        raise ValueError(f"unknown preconditioner {precond!r}")
+    if precond != "none" and not use_cg:
+        raise ValueError("a preconditioner needs the CG solve (use_cg)")
+    jacobi = precond == "jacobi"
     rank0 = pb.comm.rank == 0
     res = BenchmarkResults()
     u = pb.assemble_rhs()
@@ -132,16 +141,21 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
         op = make_operator(pb, kernel, geometry)
         if pb.platform == "gpu":
             torch.cuda.synchronize()
-    dev_cg = DeviceCG(pb) if (use_cg and pb.platform == "gpu") else None
+    dev_cg = None
+    if use_cg and pb.platform == "gpu":
+        dev_cg = DeviceCG(pb, "jacobi") if jacobi else DeviceCG(pb)
+    dinv = pb.jacobi_inverse() if jacobi else None
     res.extra["kernel"] = getattr(op, "name", type(op).__name__)
     res.extra["geometry"] = getattr(op, "geometry", "otf")
+    if jacobi:  # the default run's JSON stays exactly what it was
+        res.extra["precond"] = precond
     if warmup > 0:
         with timed("~warmup"):
-            _run_loop(op, pb, y, u, warmup, use_cg, dev_cg)
+            _run_loop(op, pb, y, u, warmup, use_cg, dev_cg, dinv)
             y.zero_()
     _sync(pb)
     t0 = time.perf_counter()
-    _run_loop(op, pb, y, u, nreps, use_cg, dev_cg)
+    _run_loop(op, pb, y, u, nreps, use_cg, dev_cg, dinv)
     _sync(pb)
     dt = time.perf_counter() - t0
     dt = pb.comm.allreduce_scalar(dt, "max")
@@ -159,10 +173,12 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
     if mat_comp:
         A = CSROperator(pb)
         z = pb.new_vector()
+        # the CSR solve takes its Jacobi diagonal from the assembled matrix itself
+        dinv_csr = torch.reciprocal(A.diagonal()) if jacobi else None
         _sync(pb)
         with timed("% CSR Matvec", sync=lambda: _sync(pb)):
             if use_cg:
-                cg_solve(A, pb, z, u, nreps, 0.0)
+                cg_solve(A, pb, z, u, nreps, 0.0, dinv=dinv_csr)
             else:
                 for _ in range(nreps):
                     A.apply(u, z)

@@ -136,6 +136,8 @@ class PoissonProblem:
         kc = cell_coefficients(self.lat, coefficient, KAPPA)
         self.kc_host = None if kc is None else np.ascontiguousarray(kc, dtype=npdt)
         self.kc = None if kc is None else torch.from_numpy(self.kc_host).to(self.device)
+        self._diag = None  # operator_diagonal() / jacobi_inverse() caches
+        self._dinv = None
 
     # --------------------------------------------------------------- vectors
     @property
@@ -230,6 +232,50 @@ class PoissonProblem:
             b.masked_fill_(self.bc_mask(), 0.0)
             self.halo.forward(b)
         return b
+
+    # ---------------------------------------------------------- diagonal
+    def operator_diagonal(self) -> torch.Tensor:
+        """diag(A) of the stiffness operator without assembling the matrix
+        (the reference reads it off the assembled CSR matrix,
+        MatrixOperator::get_diag_inverse, src/csr.hpp:81-106).
+
+        Lattice-shaped, in the problem's dtype and on its device: the
+        sum-factorised element diagonals of all local cells (lap_diag.h on the
+        GPU, its host twin on the CPU; no atomics, bitwise reproducible),
+        reverse-exchanged so owners hold the full sum, Dirichlet entries set
+        to 1 (the operators put the identity on those rows), then
+        forward-exchanged to the ghosts.  Storage padding holds 1, so a
+        reciprocal over the whole storage is finite.  Cached.
+
+        A property of the problem (mesh, kappa, tables), so it serves every
+        operator in the problem's own numbering, `dofmap` included.  Out of
+        scope: operators built on an explicitly renumbered `UnstructuredMesh`.
+        """
+        if self._diag is None:
+            with timed("~setup diagonal"):
+                d = torch.ones(self.lat.shape, dtype=self.dtype, device=self.device)
+                d[:, :, : self.lat.L[2]] = 0
+                lo = np.zeros(3, dtype=np.int64)
+                hi = np.array(self.lat.n, dtype=np.int64)
+                if self.platform == "gpu":
+                    self.kernels.diagonal(self.xv, self.kappa, self.kc, d, lo, hi)
+                else:
+                    t = self.host_tables
+                    getattr(native.host(), f"bdx_cpu_diag_{self.suf}")(
+                        ptr(self.latd), self.tables.nq, ptr(t["B"]), ptr(t["Dd"]), ptr(t["wts"]),
+                        ptr(t["qpts"]), ptr(self.xv_host), self.kappa, ptr(self.kc_host),
+                        ptr(d.numpy()), ptr(lo), ptr(hi))
+                self.halo.reverse(d)
+                d.masked_fill_(self.bc_mask(), 1.0)
+                self.halo.forward(d)
+                self._diag = d
+        return self._diag
+
+    def jacobi_inverse(self) -> torch.Tensor:
+        """1 / operator_diagonal(): the Jacobi preconditioner (cached)."""
+        if self._dinv is None:
+            self._dinv = torch.reciprocal(self.operator_diagonal())
+        return self._dinv
 
     @property
     def ndofs_global(self) -> int:
@@ -386,6 +432,24 @@ class CSROperator:
     def frobenius_norm(self) -> float:
         s = float(torch.sum(self.vals.double() ** 2).item())
         return math.sqrt(self.pb.comm.allreduce_scalar(s))
+
+    def diagonal(self) -> torch.Tensor:
+        """diag(A) extracted from the assembled matrix (the reference's
+        compute_diag_inv reads the same entries, src/csr.hpp:81-106):
+        lattice-shaped, ghost rows' partial sums reverse-accumulated to the
+        owners like any vector, then forwarded; storage padding holds 1."""
+        pb, lat = self.pb, self.pb.lat
+        row_ptr, cols, vals = self._host
+        rows = np.repeat(np.arange(lat.nstore, dtype=np.int64), np.diff(row_ptr))
+        on = rows == cols
+        d = np.zeros(lat.nstore, dtype=vals.dtype)
+        d[rows[on]] = vals[on]
+        d = d.reshape(lat.shape)
+        d[:, :, lat.L[2]:] = 1
+        d = torch.from_numpy(d).to(pb.device)
+        pb.halo.reverse(d)
+        pb.halo.forward(d)
+        return d
 
     def _spmv(self, beg, end, x, y, acc):
         pb = self.pb

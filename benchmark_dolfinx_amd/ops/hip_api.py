@@ -26,6 +26,12 @@ def declare(lib) -> None:
         _d(lib, f"bdx_cg_update_{suf}",
            [i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp])
         _d(lib, f"bdx_p_update_{suf}", [i64, i64, i64, i64, i64, vp, vp, vp, i32, i32, vp])
+        _d(lib, f"bdx_pcg_update_{suf}",
+           [i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp])
+        _d(lib, f"bdx_pcg_p_update_{suf}",
+           [i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, i32, vp])
+        _d(lib, f"bdx_diag_{suf}",
+           [vp, i32, vp, vp, vp, vp, i32, vp, f64, vp, vp, vp, vp, vp])
         _d(lib, f"bdx_axpy_{suf}", [i64, i64, i64, i64, i64, vp, f64, vp, vp, vp])
         _d(lib, f"bdx_box_copy_{suf}", [i32, vp, i64, i64, vp, i32, i64, vp, vp])
         _d(lib, f"bdx_box_copy_lat_{suf}", [i32, vp, vp, vp, i32, i64, vp, vp])

@@ -72,6 +72,16 @@ class HipKernels:
                                        ptr(G), ptr(xv), kappa, ptr(kc), ptr(u), ptr(y), ptr(lo),
                                        ptr(hi), _stream()), "v1_apply")
 
+    def diagonal(self, xv, kappa: float, kc, d, lo, hi):
+        """d += matrix-free diag(A) of the cells [lo, hi) (lap_diag.h; Dirichlet
+        dofs skipped, no atomics: eight colour launches in a fixed order)."""
+        lo = np.asarray(lo, dtype=np.int64)
+        hi = np.asarray(hi, dtype=np.int64)
+        t = self.t
+        _check(self._f("bdx_diag")(ptr(self.latd), t.nq, ptr(t.phi0), ptr(t.dphi1), ptr(t.wts),
+                                   ptr(t.qpts), t.identity, ptr(xv), kappa, ptr(kc), ptr(d),
+                                   ptr(lo), ptr(hi), _stream()), "diagonal")
+
     def dofmap_tables(self, device):
         """Device copy of the 1D tables the dofmap kernels read:
         [phi0 (nq x nd) | dphi1 (nq x nq) | qpts | wts | Dd = dphi1 phi0 (nq x nd) |
@@ -153,6 +163,22 @@ class HipKernels:
         _check(self._f("bdx_p_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
                                        ptr(p), ptr(r), ptr(scal), num, den, _stream()),
                "p_update")
+
+    def pcg_update(self, x, r, p, y, dinv, scal, rz_slot, pap_slot, out_slot, rr_slot, partials):
+        """Jacobi PCG: alpha = s[rz] / s[pap]; x += alpha p; r -= alpha y;
+        s[out] = sum dinv r^2 (the new r.z), s[rr] = sum r^2."""
+        L = self.lat
+        _check(self._f("bdx_pcg_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
+                                         ptr(x), ptr(r), ptr(p), ptr(y), ptr(dinv), ptr(scal),
+                                         rz_slot, pap_slot, out_slot, rr_slot, ptr(partials),
+                                         _stream()), "pcg_update")
+
+    def pcg_p_update(self, p, r, dinv, scal, num, den):
+        """p = (s[num] / s[den]) p + dinv . r."""
+        L = self.lat
+        _check(self._f("bdx_pcg_p_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
+                                           ptr(p), ptr(r), ptr(dinv), ptr(scal), num, den,
+                                           _stream()), "pcg_p_update")
 
     def axpy(self, out, alpha: float, x, y):
         L = self.lat

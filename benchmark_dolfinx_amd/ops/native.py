@@ -74,6 +74,8 @@ def host():
                 _declare(lib, f"bdx_cpu_dofmap_geometry_{suf}", [i32, i32, vp, vp, i32, vp, vp, vp])
                 _declare(lib, f"bdx_cpu_mass_{suf}",
                          [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp])
+                _declare(lib, f"bdx_cpu_diag_{suf}",
+                         [vp, i32, vp, vp, vp, vp, vp, ft, vp, vp, vp, vp])
                 _declare(lib, f"bdx_cpu_csr_{suf}",
                          [vp, i32, vp, vp, vp, vp, vp, ft, vp, vp, vp, vp, i32], i64)
                 _declare(lib, f"bdx_cpu_spmv_{suf}", [i64, vp, vp, vp, vp, vp, vp, i32])

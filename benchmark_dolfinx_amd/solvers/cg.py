@@ -1,4 +1,6 @@
-"""Unpreconditioned conjugate gradients (reference: `cg_solve`, src/cg.hpp:89-169).
+"""Conjugate gradients (reference: `cg_solve`, src/cg.hpp:89-169), unpreconditioned
+by default, optionally Jacobi-preconditioned with the matrix-free diagonal
+(`cg_solve(..., dinv=...)`, `DeviceCG(pb, precond="jacobi")`).
 
 Two implementations with the reference's algorithm (x0 given, r0 = b - A x0,
 p0 = r0, rtol = 0 runs exactly max_iter iterations):
@@ -23,7 +25,11 @@ import torch
 
 
 def cg_solve(op, pb, x: torch.Tensor, b: torch.Tensor, max_iter: int,
-             rtol: float = 0.0) -> int:
+             rtol: float = 0.0, dinv: torch.Tensor | None = None) -> int:
+    """`dinv` (lattice-shaped 1 / diag(A), `PoissonProblem.jacobi_inverse`):
+    Jacobi-preconditioned CG; None: the unpreconditioned algorithm."""
+    if dinv is not None:
+        return _pcg_solve(op, pb, x, b, max_iter, rtol, dinv)
     r = pb.new_vector()
     y = pb.new_vector()
     op.apply(x, y)
@@ -48,17 +54,60 @@ def cg_solve(op, pb, x: torch.Tensor, b: torch.Tensor, max_iter: int,
     return k
 
 
+def _pcg_solve(op, pb, x, b, max_iter: int, rtol: float, dinv) -> int:
+    """Standard PCG with M^-1 = diag(dinv): z = dinv . r, beta = r.z (new) /
+    r.z (old), stop test on r.r (the reference's hook for it:
+    MatrixOperator::get_diag_inverse, src/csr.hpp:81-106)."""
+    r = pb.new_vector()
+    y = pb.new_vector()
+    op.apply(x, y)
+    r.copy_(b - y)
+    z = dinv * r
+    p = z.clone()
+    rz = pb.inner(r, z)
+    rtol2 = rtol * rtol
+    rnorm0 = pb.inner(r, r) if rtol2 > 0 else 0.0
+    k = 0
+    while k < max_iter:
+        k += 1
+        op.apply(p, y)
+        alpha = rz / pb.inner(p, y)
+        x.add_(p, alpha=alpha)
+        r.add_(y, alpha=-alpha)
+        torch.mul(dinv, r, out=z)
+        rz_new = pb.inner(r, z)
+        beta = rz_new / rz
+        rz = rz_new
+        if rnorm0 > 0 and pb.inner(r, r) / rnorm0 < rtol2:
+            break
+        p.mul_(beta).add_(z)
+    return k
+
+
 class DeviceCG:
-    """Device-resident CG state for the GPU platform."""
+    """Device-resident CG state for the GPU platform.
+
+    precond="jacobi": Jacobi-preconditioned CG with the problem's matrix-free
+    diagonal.  It always runs the generic loop (op.apply + dot + pcg_update +
+    pcg_p_update, z = dinv . r never stored), also for operators that offer a
+    fused `cg_start` / `cg_iterate`."""
 
     # float64 scalar slots
     RR0, RR1, PAP = 0, 1, 2
+    # Jacobi PCG: RR0 / RR1 carry r.z, RNORM the plain r.r; ZERO / ONE give the
+    # prologue's beta = 0 (slots 3, 4: the fused kernels' lagged alphas)
+    RNORM, ZERO, ONE = 5, 6, 7
 
-    def __init__(self, pb):
+    def __init__(self, pb, precond: str | None = None):
+        if precond not in (None, "jacobi"):
+            raise ValueError(f"unknown preconditioner {precond!r}")
+        self.dinv = pb.jacobi_inverse() if precond == "jacobi" else None
         self.pb = pb
         self.k = pb.kernels
         dev = pb.device
         self.scal = torch.zeros(8, dtype=torch.float64, device=dev)
+        if precond == "jacobi":
+            self.scal[self.ONE] = 1.0
         self.partials = torch.zeros(self.k.npart, dtype=torch.float64, device=dev)
         self.r = pb.new_vector()
         self.y = pb.new_vector()
@@ -71,10 +120,21 @@ class DeviceCG:
     def start(self, op, x: torch.Tensor, b: torch.Tensor) -> None:
         """r0 = b - A x0, p0 = r0, rho0 = p0.r0 (the prologue of src/cg.hpp:98-112)."""
         self.op, self.x, self.it = op, x, 0
+        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
+        if self.dinv is not None:
+            # p0 = dinv . r0 (beta = 0 / 1), rz0 = p0.r0, rr0 = r0.r0
+            op.apply(x, y)
+            k.axpy(r, -1.0, y, b)
+            p.zero_()
+            k.pcg_p_update(p, r, self.dinv, scal, self.ZERO, self.ONE)
+            k.dot(p, r, self.partials, scal, self.RR0)
+            self._allreduce(self.RR0)
+            k.dot(r, r, self.partials, scal, self.RNORM)
+            self._allreduce(self.RNORM)
+            return
         if hasattr(op, "cg_start"):
             op.cg_start(self, x, b)
             return
-        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
         op.apply(x, y)
         k.axpy(r, -1.0, y, b)
         p.copy_(r)
@@ -86,10 +146,25 @@ class DeviceCG:
         operator lags its x update by one iteration; `flush=False` leaves the
         last one pending for the next call (x is then one update behind)."""
         op, x = self.op, self.x
+        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
+        if self.dinv is not None:
+            dinv = self.dinv
+            for _ in range(n):
+                cur = self.RR0 if self.it % 2 == 0 else self.RR1
+                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
+                op.apply(p, y)
+                k.dot(p, y, self.partials, scal, self.PAP)
+                self._allreduce(self.PAP)
+                k.pcg_update(x, r, p, y, dinv, scal, cur, self.PAP, nxt, self.RNORM,
+                             self.partials)
+                self._allreduce(nxt)
+                self._allreduce(self.RNORM)
+                k.pcg_p_update(p, r, dinv, scal, nxt, cur)
+                self.it += 1
+            return
         if hasattr(op, "cg_iterate"):
             op.cg_iterate(self, n, flush=flush)
             return
-        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
         for _ in range(n):
             cur = self.RR0 if self.it % 2 == 0 else self.RR1
             nxt = self.RR1 if self.it % 2 == 0 else self.RR0
@@ -105,7 +180,7 @@ class DeviceCG:
         """iterate(n) plus the device time (ms) of each step.  The native
         runtime records timing events between its steps (same launches as
         iterate); the Python loop records torch events around each step."""
-        rt = getattr(self.op, "_rt", None)
+        rt = getattr(self.op, "_rt", None) if self.dinv is None else None
         if rt is not None:
             return rt.iterate_timed(n)
         if self.pb.platform != "gpu":
@@ -125,7 +200,7 @@ class DeviceCG:
         """Host wait for the queued iterations.  With the native runtime the
         wait is bounded by the RCCL deadline (a hung peer raises instead of
         blocking torch.cuda.synchronize forever)."""
-        rt = getattr(self.op, "_rt", None)
+        rt = getattr(self.op, "_rt", None) if self.dinv is None else None
         if rt is not None:
             rt.wait()
         elif self.pb.platform == "gpu":
@@ -137,6 +212,8 @@ class DeviceCG:
         return max_iter
 
     def residual_norm2(self) -> float:
+        if self.dinv is not None:
+            return float(self.scal[self.RNORM].item())
         slot = self.RR0 if self.it % 2 == 0 else self.RR1
         return float(self.scal[slot].item())
 
