@@ -12,7 +12,9 @@ Reference options (src/main.cpp:144-183): --platform, --float, --ndofs,
 MI355X extensions (additive): --kernel {auto,fused5,fused3,fused2,
 fused,v1,dofmap}, --geometry {auto,otf,otf-general,stored}, --kappa {constant,random},
 --warmup N (untimed repetitions before the timed loop), --precond {none,jacobi}
-(with --cg: Jacobi-preconditioned CG with the matrix-free operator diagonal).
+(with --cg: Jacobi-preconditioned CG with the matrix-free operator diagonal),
+--pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
+device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
 unchanged.
 """
@@ -72,6 +74,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--precond", default="none", choices=["none", "jacobi"],
                     help="CG preconditioner (needs --cg): jacobi = the inverse of the "
                          "matrix-free operator diagonal")
+    ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
+                    help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
+                         "operator apply + vector kernels; fused = the fused operators' CG "
+                         "fusion driven by the native runtime (GPU platform, fused2/3/5)")
     return ap
 
 
@@ -86,6 +92,10 @@ def parse_args(argv=None):
         raise SystemExit("error: Invalid qmode.")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
+    if args.pcg_loop == "fused" and not args.cg:
+        raise SystemExit("error: Option 'pcg_loop fused' needs 'cg'")
+    if args.pcg_loop == "fused" and args.precond != "jacobi":
+        raise SystemExit("error: Option 'pcg_loop fused' needs 'precond jacobi'")
     return args, unknown
 
 
@@ -105,6 +115,8 @@ def main(argv=None) -> int:
         platform = "gpu" if torch.cuda.is_available() else "cpu"
     if platform not in ("cpu", "gpu"):
         raise RuntimeError("Invalid platform: " + platform)
+    if args.pcg_loop == "fused" and platform != "gpu":
+        raise SystemExit("error: Option 'pcg_loop fused' needs the gpu platform")
     comm = init_distributed(platform)
     log = init_logging(unknown, comm.rank)
     size = comm.size
@@ -176,7 +188,8 @@ def run_benchmark(comm, nx, args, platform):
     pb = PoissonProblem(comm, nx, args.degree, args.qmode, args.use_gauss, dtype,
                         platform, args.geom_perturb_fact, args.kappa)
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
-                         geometry=args.geometry, warmup=args.warmup, precond=args.precond)
+                         geometry=args.geometry, warmup=args.warmup, precond=args.precond,
+                         pcg_loop=args.pcg_loop)
     t = res.mat_free_time
     gdofs = pb.ndofs_global * args.nreps / (1e9 * t) if t > 0 else 0.0
     out = {"ncells_global": pb.ncells_global, "ndofs_global": pb.ndofs_global,

@@ -34,6 +34,24 @@ constexpr int kUpdGrid = kPartialsCap - kStage1;  // update pass grid cap
 constexpr int kUpdU = 2;  // vectors per thread of the tiled update pass
 constexpr bool kUpdPre = true;  // cg_update_tiled_pre_kernel (interface loads issued up front)
 
+// The extra arguments of the Jacobi-preconditioned update passes (PC below):
+// the update kernels take them as an optional trailing argument, so the
+// unpreconditioned instances (no such argument) are the kernels they were.
+template <typename T>
+struct PcArgs {
+  const T* dinv;        // 1 / diag(A), in the layout of r
+  T* z;                 // z = dinv . r, in the layout of r
+  double* partials_rr;  // block partials of r.r (`partials` carries r.z)
+};
+template <typename T>
+__device__ __forceinline__ PcArgs<T> pc_args() {
+  return PcArgs<T>{nullptr, nullptr, nullptr};
+}
+template <typename T>
+__device__ __forceinline__ PcArgs<T> pc_args(PcArgs<T> a) {
+  return a;
+}
+
 // CG update of the fused2..5 paths: alpha = s[rn] / s[pap];
 //   r -= alpha (y + interface partials);  partial r.r
 // The tile-interface partials (YB/ZB/CB) are folded here on the fly instead of
@@ -47,14 +65,24 @@ constexpr bool kUpdPre = true;  // cg_update_tiled_pre_kernel (interface loads i
 // blocks up to the partials capacity (grid-stride beyond), both loads of a
 // thread in flight before any arithmetic.  Same arithmetic per element as the
 // row kernel above (fold, r update, r.r); columns k >= o2 are left as read.
-template <typename T>
+//
+// PC (Jacobi-preconditioned CG, bdx_pcg_update_*): the same fold and r update,
+// bit for bit; the pass also streams dinv (loaded with y and r, before any
+// arithmetic), stores z = dinv . r for every vector it stores r for (all W
+// lanes: the lanes the r update leaves as read carry dinv times the r read,
+// ghost planes of z are overwritten by the next forward exchange), and sums
+// r.z into `partials` and r.r into `partials_rr` over the owned nodes.
+// Without the trailing PcArgs this is the unpreconditioned pass.
+template <typename T, typename... PA>
 __global__ void __launch_bounds__(256)
     cg_update_flat_kernel(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,
                           int64_t Lz, T* __restrict__ r, const T* __restrict__ y,
                           const T* __restrict__ yb, const T* __restrict__ zb,
                           const T* __restrict__ cb, int nty, int ntz, int sy, int sz,
                           const double* __restrict__ scal, int rn_slot, int pap_slot,
-                          double* __restrict__ partials) {
+                          double* __restrict__ partials, PA... pa) {
+  constexpr bool PC = sizeof...(PA) != 0;
+  [[maybe_unused]] const PcArgs<T> pc = pc_args<T>(pa...);
   __shared__ double lds[16];
   const T alpha = static_cast<T>(scal[rn_slot] / scal[pap_slot]);
   constexpr int W = 16 / sizeof(T), U = 2, CH = 256 * U;
@@ -66,16 +94,20 @@ __global__ void __launch_bounds__(256)
   const float inv_sz = 1.0f / static_cast<float>(sz);
   const float inv_ldv = 1.0f / static_cast<float>(ldv);
   double acc = 0.0;
+  [[maybe_unused]] double acc_rr = 0.0;
   for (int64_t c = blockIdx.x; c < nwork; c += gridDim.x) {
     const int64_t i = c / nch;
     const int v0 = static_cast<int>(c - i * nch) * CH + static_cast<int>(threadIdx.x) * U;
     const int64_t pbase = i * L1 * ld;
     V vy[U], vr[U];
+    [[maybe_unused]] V vd[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (v0 + u < nvp) {
         vy[u] = ld_stream(reinterpret_cast<const V*>(y + pbase + static_cast<int64_t>(v0 + u) * W));
         vr[u] = ld_stream(reinterpret_cast<const V*>(r + pbase + static_cast<int64_t>(v0 + u) * W));
+        if constexpr (PC)
+          vd[u] = ld_stream(reinterpret_cast<const V*>(pc.dinv + pbase + static_cast<int64_t>(v0 + u) * W));
       }
     }
 #pragma unroll
@@ -103,13 +135,26 @@ __global__ void __launch_bounds__(256)
         }
         const T rn = vr[u][e] - alpha * t;
         vr[u][e] = rn;
-        acc += static_cast<double>(rn) * static_cast<double>(rn);
+        if constexpr (PC) {
+          const T zn = vd[u][e] * rn;  // the value stored below
+          acc += static_cast<double>(rn) * static_cast<double>(zn);
+          acc_rr += static_cast<double>(rn) * static_cast<double>(rn);
+        } else {
+          acc += static_cast<double>(rn) * static_cast<double>(rn);
+        }
       }
       st_stream(reinterpret_cast<V*>(r + pbase + static_cast<int64_t>(v) * W), vr[u]);
+      if constexpr (PC)
+        st_stream(reinterpret_cast<V*>(pc.z + pbase + static_cast<int64_t>(v) * W), vd[u] * vr[u]);
     }
   }
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  if constexpr (PC) {
+    __shared__ double lds_rr[16];
+    const double t2 = block_sum(acc_rr, lds_rr);
+    if (threadIdx.x == 0) pc.partials_rr[blockIdx.x] = t2;
+  }
 }
 
 // The r update of the tiled storage (bdx_lattice.h, tsy != 0): the same
@@ -132,14 +177,18 @@ __global__ void __launch_bounds__(256)
 // non-temporal (whole 16-byte vectors, full lines; unlike the operator's
 // march, nothing here relies on L2 merging partial rows): update Q3 1.53 ->
 // 1.46 ms, Q6 FP64 2.50 -> 2.30, +1.6-1.8 % GDoF/s same box (same file).
-template <typename T, bool ROW, int U>
+// PC: the preconditioned pass (see cg_update_flat_kernel): dinv streamed with y
+// and r, z = dinv . r stored wherever r is stored, r.z and r.r summed.
+template <typename T, bool ROW, int U, typename... PA>
 __global__ void __launch_bounds__(256)
     cg_update_tiled_kernel(int64_t L0, int64_t L1, int64_t Lz, int tsy, int tsz, int tntz,
                            int64_t o0, int64_t o1, int64_t o2, int64_t nvec, T* __restrict__ r,
                            const T* __restrict__ y, const T* __restrict__ yb,
                            const T* __restrict__ zb, const T* __restrict__ cb, int nty, int ntz,
                            const double* __restrict__ scal, int rn_slot, int pap_slot,
-                           double* __restrict__ partials) {
+                           double* __restrict__ partials, PA... pa) {
+  constexpr bool PC = sizeof...(PA) != 0;
+  [[maybe_unused]] const PcArgs<T> pc = pc_args<T>(pa...);
   __shared__ double lds[16];
   const T alpha = static_cast<T>(scal[rn_slot] / scal[pap_slot]);
   constexpr int W = 16 / sizeof(T);
@@ -150,17 +199,21 @@ __global__ void __launch_bounds__(256)
   const float inv_tsz = 1.0f / static_cast<float>(tsz);
   const int l0 = static_cast<int>(L0);
   double acc = 0.0;
+  [[maybe_unused]] double acc_rr = 0.0;
   for (int64_t vb = static_cast<int64_t>(blockIdx.x) * (256 * U) + threadIdx.x; vb < nvec;
        vb += static_cast<int64_t>(gridDim.x) * (256 * U)) {
     // U vectors per thread, 256 apart (each load coalesced over the block), all
     // loads in flight before the index math and the arithmetic
     V vyu[U], vru[U];
+    [[maybe_unused]] V vdu[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t v = vb + u * 256;
       if (v < nvec) {
         vyu[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(y + v * W));
         vru[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(r + v * W));
+        if constexpr (PC)
+          vdu[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(pc.dinv + v * W));
       }
     }
 #pragma unroll
@@ -211,10 +264,17 @@ __global__ void __launch_bounds__(256)
           const T rn = vr[w] - alpha * t[w];
           if (w < nw) {
             vr[w] = rn;
-            acc += static_cast<double>(rn) * static_cast<double>(rn);
+            if constexpr (PC) {
+              const T zn = vdu[u][w] * rn;  // the value stored below
+              acc += static_cast<double>(rn) * static_cast<double>(zn);
+              acc_rr += static_cast<double>(rn) * static_cast<double>(rn);
+            } else {
+              acc += static_cast<double>(rn) * static_cast<double>(rn);
+            }
           }
         }
         __builtin_nontemporal_store(vr, reinterpret_cast<V*>(r + e0));
+        if constexpr (PC) __builtin_nontemporal_store(vdu[u] * vr, reinterpret_cast<V*>(pc.z + e0));
       } else {
         const V vy = vyu[u];
         V vr = vru[u];
@@ -239,14 +299,28 @@ __global__ void __launch_bounds__(256)
           }
           const T rn = vr[w] - alpha * t;
           vr[w] = rn;
-          acc += static_cast<double>(rn) * static_cast<double>(rn);
+          if constexpr (PC) {
+            const T zn = vdu[u][w] * rn;  // the value stored below
+            acc += static_cast<double>(rn) * static_cast<double>(zn);
+            acc_rr += static_cast<double>(rn) * static_cast<double>(rn);
+          } else {
+            acc += static_cast<double>(rn) * static_cast<double>(rn);
+          }
         }
         if (any) __builtin_nontemporal_store(vr, reinterpret_cast<V*>(r + e0));
+        if constexpr (PC) {
+          if (any) __builtin_nontemporal_store(vdu[u] * vr, reinterpret_cast<V*>(pc.z + e0));
+        }
       }
     }
   }
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  if constexpr (PC) {
+    __shared__ double lds_rr[16];
+    const double t2 = block_sum(acc_rr, lds_rr);
+    if (threadIdx.x == 0) pc.partials_rr[blockIdx.x] = t2;
+  }
 }
 
 // The tiled r update with the tile-interface partials loaded together with
@@ -258,13 +332,17 @@ __global__ void __launch_bounds__(256)
 // buffer loads whose offset is out of range (the load returns 0, no memory
 // access) where an element has no such term; the arithmetic follows.  Same
 // sums in the same order as cg_update_tiled_kernel.
-template <typename T, bool ROW, int U>
+// PC: the preconditioned pass (see cg_update_flat_kernel); dinv is loaded with y
+// and r, ahead of the interface loads.
+template <typename T, bool ROW, int U, typename... PA>
 __global__ void __launch_bounds__(256)
     cg_update_tiled_pre_kernel(int64_t L0, int64_t L1, int64_t Lz, int tsy, int tsz, int tntz,
                                int64_t o0, int64_t o1, int64_t o2, int64_t nvec, T* __restrict__ r,
                                const T* __restrict__ y, const T* yb, const T* zb, const T* cb,
                                int nty, int ntz, const double* __restrict__ scal, int rn_slot,
-                               int pap_slot, double* __restrict__ partials) {
+                               int pap_slot, double* __restrict__ partials, PA... pa) {
+  constexpr bool PC = sizeof...(PA) != 0;
+  [[maybe_unused]] const PcArgs<T> pc = pc_args<T>(pa...);
   __shared__ double lds[16];
   const T alpha = static_cast<T>(scal[rn_slot] / scal[pap_slot]);
   constexpr int W = 16 / sizeof(T);
@@ -291,9 +369,11 @@ __global__ void __launch_bounds__(256)
   const float inv_tsz = 1.0f / static_cast<float>(tsz);
   const int l0 = static_cast<int>(L0);
   double acc = 0.0;
+  [[maybe_unused]] double acc_rr = 0.0;
   for (int64_t vb = static_cast<int64_t>(blockIdx.x) * (256 * U) + threadIdx.x; vb < nvec;
        vb += static_cast<int64_t>(gridDim.x) * (256 * U)) {
     V vyu[U], vru[U];
+    [[maybe_unused]] V vdu[U];
     T ia[U][NI];
     int own[U];  // bit w: element w is owned
 #pragma unroll
@@ -305,6 +385,8 @@ __global__ void __launch_bounds__(256)
       if (v >= nvec) continue;
       vyu[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(y + v * W));
       vru[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(r + v * W));
+      if constexpr (PC)
+        vdu[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(pc.dinv + v * W));
       const int64_t e0 = v * W;
       int64_t c = static_cast<int64_t>(static_cast<double>(e0) * inv_ch);  // chunk
       if (c * ch > e0) --c;
@@ -388,14 +470,26 @@ __global__ void __launch_bounds__(256)
         const T rn = vr[w] - alpha * t;
         if (own[u] & (1 << w)) {
           vr[w] = rn;
-          acc += static_cast<double>(rn) * static_cast<double>(rn);
+          if constexpr (PC) {
+            const T zn = vdu[u][w] * rn;  // the value stored below
+            acc += static_cast<double>(rn) * static_cast<double>(zn);
+            acc_rr += static_cast<double>(rn) * static_cast<double>(rn);
+          } else {
+            acc += static_cast<double>(rn) * static_cast<double>(rn);
+          }
         }
       }
       __builtin_nontemporal_store(vr, reinterpret_cast<V*>(r + v * W));
+      if constexpr (PC) __builtin_nontemporal_store(vdu[u] * vr, reinterpret_cast<V*>(pc.z + v * W));
     }
   }
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  if constexpr (PC) {
+    __shared__ double lds_rr[16];
+    const double t2 = block_sum(acc_rr, lds_rr);
+    if (threadIdx.x == 0) pc.partials_rr[blockIdx.x] = t2;
+  }
 }
 
 // x += (s[num] / s[den]) p over the owned rows (flush of the lagged x update).
@@ -533,6 +627,96 @@ BDX_CGI(float, f32)
 BDX_CGT(double, f64)
 BDX_CGT(float, f32)
 #undef BDX_CGT
+
+}  // extern "C"
+
+// Fixed-order sum of the g block partials of an update pass into scal[slot]
+// (the two-stage scheme of the unpreconditioned entry points above).
+static void reduce_update_partials(double* partials, int g, double* scal, int slot,
+                                   hipStream_t st) {
+  if (g > 4 * kStage1) {
+    double* stage = partials + kPartialsCap - kStage1;
+    reduce_partials_slices<<<kStage1, 256, 0, st>>>(partials, g, stage);
+    reduce_partials_fixed<<<1, 256, 0, st>>>(stage, kStage1, scal, slot);
+  } else {
+    reduce_partials_fixed<<<1, 256, 0, st>>>(partials, g, scal, slot);
+  }
+}
+
+extern "C" {
+
+// Jacobi-preconditioned r update of the fused CG loop, lattice layout:
+// bdx_cg_update_iface_* (same fold, same r, bit for bit) plus z = dinv . r
+// stored for every vector r is stored for, r.z -> scal[out_slot] and
+// r.r -> scal[rr_slot] over the owned nodes.  partials_rr: a second buffer of
+// bdx_hip_partials_size() doubles; both sums are reduced in fixed order.
+#define BDX_PCGI(T, SUF)                                                                  \
+  int bdx_pcg_update_iface_##SUF(const int64_t* latd, const int64_t* own, T* r,          \
+                                 const T* y, const T* yb, const T* zb, const T* cb,      \
+                                 int nty, int ntz, int sy, int sz, double* scal,         \
+                                 int rn_slot, int pap_slot, int out_slot,                \
+                                 double* partials, const T* dinv, T* z, int rr_slot,     \
+                                 double* partials_rr, hipStream_t st) {                  \
+    if (!dinv || !z || !partials_rr || partials_rr == partials || rr_slot == out_slot)   \
+      return static_cast<int>(hipErrorInvalidValue);                                     \
+    const BdxLattice lat = BdxLattice::from(latd);                                       \
+    const int64_t nvp = own[1] * (lat.ld * static_cast<int64_t>(sizeof(T)) / 16);        \
+    const int64_t want = own[0] * ((nvp + 511) / 512);                                   \
+    const int g = static_cast<int>(want < kUpdGrid ? (want > 0 ? want : 1) : kUpdGrid);  \
+    cg_update_flat_kernel<T, PcArgs<T>><<<g, 256, 0, st>>>(                              \
+        lat.L[1], lat.ld, own[0], own[1], own[2], lat.L[2], r, y, yb, zb, cb, nty, ntz,  \
+        sy, sz, scal, rn_slot, pap_slot, partials, PcArgs<T>{dinv, z, partials_rr});     \
+    reduce_update_partials(partials, g, scal, out_slot, st);                             \
+    reduce_update_partials(partials_rr, g, scal, rr_slot, st);                           \
+    return static_cast<int>(hipGetLastError());                                          \
+  }
+BDX_PCGI(double, f64)
+BDX_PCGI(float, f32)
+#undef BDX_PCGI
+
+// The same on the tiled storage (latd: the tiled descriptor; dinv and z in
+// tiled storage too): the kernel selection of bdx_cg_update_tiled_* -- the
+// BDX_UPD_PLAIN hook and the 31-bit guard of the prefetching kernel included.
+#define BDX_PCGT(T, SUF)                                                                        \
+  int bdx_pcg_update_tiled_##SUF(const int64_t* latd, const int64_t* own, T* r, const T* y,    \
+                                 const T* yb, const T* zb, const T* cb, int nty, int ntz,      \
+                                 double* scal, int rn_slot, int pap_slot, int out_slot,        \
+                                 double* partials, const T* dinv, T* z, int rr_slot,           \
+                                 double* partials_rr, hipStream_t st) {                        \
+    if (!dinv || !z || !partials_rr || partials_rr == partials || rr_slot == out_slot)         \
+      return static_cast<int>(hipErrorInvalidValue);                                           \
+    const BdxLattice L = BdxLattice::from(latd);                                               \
+    if (!L.tsy || (L.tsy * L.tsz * static_cast<int64_t>(sizeof(T))) % 16)                     \
+      return static_cast<int>(hipErrorInvalidValue);                                           \
+    const int64_t nvec = L.size() / (16 / static_cast<int64_t>(sizeof(T)));                    \
+    const int64_t want = (nvec + 256 * kUpdU - 1) / (256 * kUpdU);                             \
+    const int g = static_cast<int>(want < kUpdGrid ? (want > 0 ? want : 1) : kUpdGrid);        \
+    const bool force_plain = std::getenv("BDX_UPD_PLAIN") != nullptr;                         \
+    const bool pre = kUpdPre && !force_plain &&                                                \
+                     L.L[0] * L.L[1] * (ntz > 1 ? ntz - 1 : 1) * 8 < (1LL << 31) &&            \
+                     L.L[0] * (nty > 1 ? nty - 1 : 1) * L.L[2] * 8 < (1LL << 31);              \
+    const bool row = sizeof(T) == 4 && L.tsz % 4 == 0;                                         \
+    auto go = [&](auto kern) {                                                                 \
+      kern<<<g, 256, 0, st>>>(L.L[0], L.L[1], L.L[2], static_cast<int>(L.tsy),                 \
+                              static_cast<int>(L.tsz), static_cast<int>(L.tntz), own[0],       \
+                              own[1], own[2], nvec, r, y, yb, zb, cb, nty, ntz, scal, rn_slot, \
+                              pap_slot, partials, PcArgs<T>{dinv, z, partials_rr});            \
+    };                                                                                         \
+    if (pre && row)                                                                            \
+      go(cg_update_tiled_pre_kernel<T, true, kUpdU, PcArgs<T>>);                               \
+    else if (pre)                                                                              \
+      go(cg_update_tiled_pre_kernel<T, false, kUpdU, PcArgs<T>>);                              \
+    else if (row)                                                                              \
+      go(cg_update_tiled_kernel<T, true, kUpdU, PcArgs<T>>);                                   \
+    else                                                                                       \
+      go(cg_update_tiled_kernel<T, false, kUpdU, PcArgs<T>>);                                  \
+    reduce_update_partials(partials, g, scal, out_slot, st);                                   \
+    reduce_update_partials(partials_rr, g, scal, rr_slot, st);                                 \
+    return static_cast<int>(hipGetLastError());                                                \
+  }
+BDX_PCGT(double, f64)
+BDX_PCGT(float, f32)
+#undef BDX_PCGT
 
 // Tile shape (cells in y, z) used by the fused kernel for a given nq.
 int bdx_fused_tile(int nq, int* ty, int* tz) {

@@ -92,6 +92,19 @@ int bdx_cg_update_tiled_f64(const int64_t*, const int64_t*, double*, const doubl
 int bdx_cg_update_tiled_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
                             const float*, const float*, int, int, double*, int, int, int, double*,
                             hipStream_t);
+int bdx_pcg_update_iface_f64(const int64_t*, const int64_t*, double*, const double*,
+                             const double*, const double*, const double*, int, int, int, int,
+                             double*, int, int, int, double*, const double*, double*, int, double*,
+                             hipStream_t);
+int bdx_pcg_update_iface_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
+                             const float*, const float*, int, int, int, int, double*, int, int,
+                             int, double*, const float*, float*, int, double*, hipStream_t);
+int bdx_pcg_update_tiled_f64(const int64_t*, const int64_t*, double*, const double*,
+                             const double*, const double*, const double*, int, int, double*, int,
+                             int, int, double*, const double*, double*, int, double*, hipStream_t);
+int bdx_pcg_update_tiled_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
+                             const float*, const float*, int, int, double*, int, int, int, double*,
+                             const float*, float*, int, double*, hipStream_t);
 }
 
 // The fused2, fused3 and fused5 operator entry points (lap_fused{2,3,5}_<suf>_p<P>.hip);
@@ -990,11 +1003,54 @@ struct CGRuntime final : LoopBase {
   const T* xv;
   const T* kc = nullptr;
   double *scal, *partials, *upart;
+  // Jacobi preconditioner binding (bdx_rt_set_precond; dinv == nullptr: none).
+  // The operator kernels form p = u + beta p_old with alpha and beta as
+  // ratios of scalar slots, so PCG is the same loop with u = z = dinv . r and
+  // r.z in the slots that carry r.r: the update pass stores z and reduces r.z
+  // into the `nxt` slot and the plain r.r into rr_slot, and the forward halo
+  // carries z.  dinvt / zt: the tiled copies (zeroed by the caller), wz /
+  // wdinv: what the loop works on.
+  const T* dinv = nullptr;
+  T* z = nullptr;
+  T *dinvt = nullptr, *zt = nullptr;
+  T* wz = nullptr;
+  const T* wdinv = nullptr;
+  double* upart_rr = nullptr;
+  int rr_slot = -1;
+  bool need_dinv_import = false;
   // overlapped schedule: tile rectangles {ty0, ty1, tz0, tz1}
   int rect_a[4], rect_r1[4], rect_r2[4];  // interior, last tile row, last tile column
 
   bool tiled() const override { return is_tiled; }
-  void* halo_vector() override { return wr; }
+  bool precond() const { return dinv != nullptr; }
+  // the vector the operator reads as u and the forward halo carries
+  T* u_vector() { return precond() ? wz : wr; }
+  void* halo_vector() override { return u_vector(); }
+
+  int set_precond(const T* d, T* zz, T* dt, T* ztl, double* prr, int slot) {
+    const hipError_t e = hipStreamSynchronize(st);
+    drop_graphs();  // they hold the update pass and the halo vector of the old binding
+    dinv = nullptr;
+    z = dinvt = zt = wz = nullptr;
+    wdinv = nullptr;
+    upart_rr = nullptr;
+    rr_slot = -1;
+    need_dinv_import = false;
+    if (!d) return static_cast<int>(e);
+    if (!zz || !prr || prr == upart || slot < 0 || slot == kRR0 || slot == kRR1 || slot == kPAP ||
+        slot == kScalXSave || slot == kScalXSave + 1 || (is_tiled && (!dt || !ztl)))
+      return static_cast<int>(hipErrorInvalidValue);
+    dinv = d;
+    z = zz;
+    dinvt = is_tiled ? dt : nullptr;
+    zt = is_tiled ? ztl : nullptr;
+    wz = is_tiled ? zt : z;
+    wdinv = is_tiled ? dinvt : dinv;
+    upart_rr = prr;
+    rr_slot = slot;
+    need_dinv_import = is_tiled;
+    return static_cast<int>(e);
+  }
 
   int convert(int dir, T* lat, T* til, hipStream_t s) {
     if constexpr (sizeof(T) == 8)
@@ -1002,12 +1058,18 @@ struct CGRuntime final : LoopBase {
     else
       return bdx_layout_convert_f32(dir, cfg.latdT, lat, til, s);
   }
-  // tiled: bring the prologue's r and x into the tiled copies, p_old = 0
+  // tiled: bring the prologue's r and x (preconditioned: and z; once per
+  // binding: dinv) into the tiled copies, p_old = 0
   int import_state() override {
     if (!is_tiled || !need_import) return 0;
     need_import = false;
     int rc;
     if ((rc = convert(0, r, rt_, st)) || (rc = convert(0, x, xt, st))) return rc;
+    if (precond()) {
+      if ((rc = convert(0, z, zt, st))) return rc;
+      if (need_dinv_import && (rc = convert(0, const_cast<T*>(dinv), dinvt, st))) return rc;
+      need_dinv_import = false;
+    }
     const BdxLattice L = BdxLattice::from(cfg.latdT);
     return static_cast<int>(hipMemsetAsync(pat, 0, L.size() * sizeof(T), st));
   }
@@ -1032,16 +1094,17 @@ struct CGRuntime final : LoopBase {
     const int m1 = stagger ? cur_m1 + 1 : 0;
     const int word = 1 | (xm << 4) | (m1 << 6) | (cfg.nseg << 8) | static_cast<int>((k & 1) << 16) |
                      static_cast<int>(((k + 1) & 1) << 17);
-    return apply(word, cfg.affine, wlatd, cfg.nq, cfg.wts.data(),
-                 cfg.qpts.data(), wr, pold, pnew, wx, wy, yb, zb, cb, xv, kc, tabs, cfg.kappa,
-                 scal, partials, first ? -1 : cur, first ? -1 : nxt, xlag ? nxt : -1,
-                 xlag ? kPAP : -1, cfg.nty, cfg.ntz, rect, s);
+    return apply(word, cfg.affine, wlatd, cfg.nq, cfg.wts.data(), cfg.qpts.data(), u_vector(),
+                 pold, pnew, wx, wy, yb, zb, cb, xv, kc, tabs, cfg.kappa, scal, partials,
+                 first ? -1 : cur, first ? -1 : nxt, xlag ? nxt : -1, xlag ? kPAP : -1, cfg.nty,
+                 cfg.ntz, rect, s);
   }
 
   int step(long k, bool first, bool xlag, int xm) override {
     const int cur = (k % 2 == 0) ? kRR0 : kRR1, nxt = cur == kRR0 ? kRR1 : kRR0;
     T* const r = wr;
     T* const y = wy;
+    T* const u = u_vector();  // forward halo: r, preconditioned: z
     auto op = [&](const int* rect, hipStream_t s) {
       return launch_op(k, first, xlag, xm, rect, s);
     };
@@ -1063,7 +1126,7 @@ struct CGRuntime final : LoopBase {
       BDX_CHECK(hipEventRecord(ev_fork, st));
       BDX_CHECK(hipStreamWaitEvent(cs, ev_fork, 0));
       mark(kMFwdBeg, cs);
-      if ((rc = halo_forward(r, cs))) return rc;
+      if ((rc = halo_forward(u, cs))) return rc;
       mark(kMFwdEnd, cs);
       if ((rc = op(rect_r1, cs)) || (rc = op(rect_r2, cs)) || (rc = finalize_ghost(cs)))
         return rc;
@@ -1083,7 +1146,7 @@ struct CGRuntime final : LoopBase {
       mark(kMJoin, st);
     } else {
       mark(kMFwdBeg, st);
-      if (halo && (rc = halo_forward(r, st))) return rc;
+      if (halo && (rc = halo_forward(u, st))) return rc;
       mark(kMFwdEnd, st);
       if ((rc = op(nullptr, st))) return rc;
       mark(kMOpA, st);
@@ -1097,7 +1160,25 @@ struct CGRuntime final : LoopBase {
     if ((rc = bdx_reduce_partials(partials, cfg.nblocks, scal, kPAP, st))) return rc;
     if (nranks > 1 && (rc = tr->allreduce_sum(scal + kPAP, 1, st))) return rc;
     mark(kMPap, st);
-    if (is_tiled) {
+    if (precond()) {
+      // r update + z = dinv . r; r.z -> nxt, r.r -> rr_slot
+      if (is_tiled) {
+        if constexpr (sizeof(T) == 8)
+          rc = bdx_pcg_update_tiled_f64(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal,
+                                        cur, kPAP, nxt, upart, wdinv, wz, rr_slot, upart_rr, st);
+        else
+          rc = bdx_pcg_update_tiled_f32(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal,
+                                        cur, kPAP, nxt, upart, wdinv, wz, rr_slot, upart_rr, st);
+      } else if constexpr (sizeof(T) == 8) {
+        rc = bdx_pcg_update_iface_f64(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
+                                      cfg.sz, scal, cur, kPAP, nxt, upart, wdinv, wz, rr_slot,
+                                      upart_rr, st);
+      } else {
+        rc = bdx_pcg_update_iface_f32(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
+                                      cfg.sz, scal, cur, kPAP, nxt, upart, wdinv, wz, rr_slot,
+                                      upart_rr, st);
+      }
+    } else if (is_tiled) {
       if constexpr (sizeof(T) == 8)
         rc = bdx_cg_update_tiled_f64(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal, cur,
                                      kPAP, nxt, upart, st);
@@ -1114,6 +1195,7 @@ struct CGRuntime final : LoopBase {
     if (rc) return rc;
     mark(kMUpd, st);
     if (nranks > 1 && (rc = tr->allreduce_sum(scal + nxt, 1, st))) return rc;
+    if (nranks > 1 && precond() && (rc = tr->allreduce_sum(scal + rr_slot, 1, st))) return rc;
     mark(kMEnd, st);
     return 0;
   }
@@ -1729,6 +1811,27 @@ int bdx_rt_bind_x(void* h, void* x) {
     if (auto* f = dynamic_cast<DofCGRuntime<double>*>(rt)) return rebind(f);
     if (auto* f = dynamic_cast<DofCGRuntime<float>*>(rt)) return rebind(f);
     return static_cast<int>(hipErrorInvalidValue);
+  });
+}
+
+// Bind (dinv != null) or clear the Jacobi preconditioner of a fused runtime:
+// dinv = 1 / diag(A) and z = dinv . r0 (the prologue's) in the lattice layout,
+// their tiled copies (zeroed by the caller; needed iff the loop is tiled), a
+// second partials buffer of bdx_hip_partials_size() doubles and the scalar
+// slot that receives the plain r.r.  The r.r slots of the unpreconditioned
+// loop then carry r.z.  Drops the captured graphs; call bdx_rt_reset after it.
+int bdx_rt_set_precond(void* h, const void* dinv, void* z, void* dinv_tiled, void* z_tiled,
+                       double* partials_rr, int rr_slot) {
+  return with_rt(h, [&](LoopBase* rt) -> int {
+    auto bind = [&](auto* f) -> int {
+      using T = std::remove_pointer_t<decltype(f->x)>;
+      return f->set_precond(static_cast<const T*>(dinv), static_cast<T*>(z),
+                            static_cast<T*>(dinv_tiled), static_cast<T*>(z_tiled), partials_rr,
+                            rr_slot);
+    };
+    if (auto* f = dynamic_cast<CGRuntime<double>*>(rt)) return bind(f);
+    if (auto* f = dynamic_cast<CGRuntime<float>*>(rt)) return bind(f);
+    return static_cast<int>(hipErrorInvalidValue);  // the dofmap loop has no such path
   });
 }
 

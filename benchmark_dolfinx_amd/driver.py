@@ -123,15 +123,24 @@ def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg, dinv=None):
 
 def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
                    kernel: str = "auto", geometry: str = "auto", warmup: int = 0,
-                   printer=print, precond: str = "none") -> BenchmarkResults:
+                   printer=print, precond: str = "none",
+                   pcg_loop: str = "generic") -> BenchmarkResults:
     """precond="jacobi" (CG only): Jacobi-preconditioned CG with the
     matrix-free diagonal; the CSR comparison solve is then preconditioned
     with the diagonal read off the assembled matrix, so the error norm
-    cross-checks the two diagonals end to end."""
+    cross-checks the two diagonals end to end.  pcg_loop="fused" (GPU,
+    precond="jacobi"): the preconditioned solve runs the fused operator's CG
+    fusion and native runtime instead of the generic device loop."""
     if precond not in ("none", "jacobi"):
         raise ValueError(f"unknown preconditioner {precond!r}")
     if precond != "none" and not use_cg:
         raise ValueError("a preconditioner needs the CG solve (use_cg)")
+    if pcg_loop not in ("generic", "fused"):
+        raise ValueError(f"unknown pcg_loop {pcg_loop!r}")
+    if pcg_loop == "fused" and not (use_cg and precond == "jacobi"):
+        raise ValueError("pcg_loop='fused' needs the CG solve with precond='jacobi'")
+    if pcg_loop == "fused" and pb.platform != "gpu":
+        raise ValueError("pcg_loop='fused' needs the gpu platform")
     jacobi = precond == "jacobi"
     rank0 = pb.comm.rank == 0
     res = BenchmarkResults()
@@ -143,12 +152,14 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
             torch.cuda.synchronize()
     dev_cg = None
     if use_cg and pb.platform == "gpu":
-        dev_cg = DeviceCG(pb, "jacobi") if jacobi else DeviceCG(pb)
+        dev_cg = DeviceCG(pb, "jacobi", loop=pcg_loop) if jacobi else DeviceCG(pb)
     dinv = pb.jacobi_inverse() if jacobi else None
     res.extra["kernel"] = getattr(op, "name", type(op).__name__)
     res.extra["geometry"] = getattr(op, "geometry", "otf")
     if jacobi:  # the default run's JSON stays exactly what it was
         res.extra["precond"] = precond
+    if pcg_loop != "generic":  # only when the option is used
+        res.extra["pcg_loop"] = pcg_loop
     if warmup > 0:
         with timed("~warmup"):
             _run_loop(op, pb, y, u, warmup, use_cg, dev_cg, dinv)

@@ -11,6 +11,12 @@ is restructured around one kernel (see lap_fused.h for the design):
 
 versus the reference's fill + pack/unpack x2 + 2 stiffness launches + 2
 Thrust reductions (host round trips) + 3 axpy launches.
+
+Jacobi-preconditioned CG (DeviceCG(pb, "jacobi", loop="fused"), fused2/3/5)
+is the same iteration with z = dinv . r in the place of r as the operator's
+input and halo vector and r.z in the r.r slots; the update pass also stores z
+and reduces the plain r.r into its own slot.  The operator kernels are the
+unpreconditioned ones.
 """
 
 from __future__ import annotations
@@ -171,6 +177,12 @@ class FusedLaplacianGPU:
         self.p_old = None
         self.p_new = None
 
+    @property
+    def supports_fused_pcg(self) -> bool:
+        """The preconditioned loop rides on the interface-folding update pass
+        of fused2/3/5 (the fused v1 loop has a separate finalize pass)."""
+        return self.version >= 2
+
     def close(self) -> None:
         """Release the native runtime (RCCL communicator, graphs, stream)
         before the process group / HIP runtime shut down."""
@@ -215,10 +227,27 @@ class FusedLaplacianGPU:
     # ------------------------------------------------------------- CG
     def cg_start(self, cg, x, b):
         k, r, y = cg.k, cg.r, cg.y
+        pc = getattr(cg, "fused_pcg", False)
+        if pc and not self.supports_fused_pcg:
+            raise ValueError(f"operator {self.name!r} has no fused preconditioned CG loop")
         self.apply(x, y)
         k.axpy(r, -1.0, y, b)
-        k.dot(r, r, cg.partials, cg.scal, cg.RR0)
-        cg._allreduce(cg.RR0)
+        if pc:
+            # z0 = dinv . r0 (beta = 0 / 1), rz0 = r0.z0 in the r.r slot, the
+            # plain r0.r0 in RNORM
+            if cg.z is None:
+                cg.z = self.pb.new_vector()
+                cg.partials_rr = torch.zeros_like(cg.partials)
+            else:
+                cg.z.zero_()
+            k.pcg_p_update(cg.z, r, cg.dinv, cg.scal, cg.ZERO, cg.ONE)
+            k.dot(cg.z, r, cg.partials, cg.scal, cg.RR0)
+            cg._allreduce(cg.RR0)
+            k.dot(r, r, cg.partials, cg.scal, cg.RNORM)
+            cg._allreduce(cg.RNORM)
+        else:
+            k.dot(r, r, cg.partials, cg.scal, cg.RR0)
+            cg._allreduce(cg.RR0)
         if self.p_old is None:
             self.p_old = self.pb.new_vector()
             self.p_new = self.pb.new_vector()
@@ -233,6 +262,8 @@ class FusedLaplacianGPU:
                     self._rt.close()
                 try:
                     self._rt = NativeCGRuntime(self, cg)
+                    if pc:  # a runtime serves one cg: the binding cannot outlive it
+                        self._rt.set_precond(cg.dinv, cg.z, cg.partials_rr, cg.RNORM)
                 except NativeRuntimeUnavailable as e:
                     # raised on every rank alike (construction is collective),
                     # so all ranks take the Python driver of the same kernels
@@ -271,19 +302,24 @@ class FusedLaplacianGPU:
         kernel's staging (lagged one iteration, flushed at the end); the tile
         interface partials are folded inside the r update (no finalize pass
         over y; with several ranks only the ghost planes are finalized, before
-        the reverse halo packs them)."""
+        the reverse halo packs them).  Preconditioned (cg.fused_pcg): the
+        operator reads and the halo carries z = dinv . r, which the update
+        pass stores, with r.z in the r.r slots and r.r in cg.RNORM."""
         r, y, x, scal = cg.r, cg.y, cg.x, cg.scal
         pb = self.pb
         halo = pb.halo
         multi = halo.active
-        upd = getattr(self.lib, f"bdx_cg_update_iface_{pb.suf}")
+        pc = getattr(cg, "fused_pcg", False)
+        u = cg.z if pc else r
+        upd = getattr(self.lib, f"bdx_{'pcg' if pc else 'cg'}_update_iface_{pb.suf}")
+        pc_args = (ptr(cg.dinv), ptr(cg.z), cg.RNORM, ptr(cg.partials_rr)) if pc else ()
         for _ in range(n):
             cur = cg.RR0 if cg.it % 2 == 0 else cg.RR1
             nxt = cg.RR1 if cg.it % 2 == 0 else cg.RR0
-            halo.forward(r)
+            halo.forward(u)
             bnum, bden = (cur, nxt) if cg.it > 0 else (-1, -1)
             xnum, xden = (nxt, cg.PAP) if self.x_lag else (-1, -1)
-            self._launch(1, r, self.p_old, self.p_new, y, scal, bnum, bden, x, xnum, xden,
+            self._launch(1, u, self.p_old, self.p_new, y, scal, bnum, bden, x, xnum, xden,
                          finalize=False)
             if multi:
                 self._finalize(y, ghost_only=True)
@@ -293,9 +329,11 @@ class FusedLaplacianGPU:
             cg._allreduce(cg.PAP)
             _check(upd(ptr(pb.latd), ptr(self._own), ptr(r), ptr(y), ptr(self.yb),
                        ptr(self.zb), ptr(self.cb), self.nty, self.ntz, self.sy, self.sz,
-                       ptr(scal), cur, cg.PAP, nxt, ptr(cg.partials), _stream()),
+                       ptr(scal), cur, cg.PAP, nxt, ptr(cg.partials), *pc_args, _stream()),
                    "cg_update_iface")
             cg._allreduce(nxt)
+            if pc:
+                cg._allreduce(cg.RNORM)
             self.p_old, self.p_new = self.p_new, self.p_old
             self.x_lag = True
             cg.it += 1

@@ -64,6 +64,10 @@ def declare(lib) -> None:
                                                 vp, i32, i32, i32, vp, vp])
         _d(lib, f"bdx_cg_update_tiled_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32, i32,
                                                 vp, i32, i32, i32, vp, vp])
+        _d(lib, f"bdx_pcg_update_iface_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32,
+                                                 vp, i32, i32, i32, vp, vp, vp, i32, vp, vp])
+        _d(lib, f"bdx_pcg_update_tiled_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                                 vp, i32, i32, i32, vp, vp, vp, i32, vp, vp])
         _d(lib, f"bdx_xflush_{suf}", [vp, vp, vp, vp, vp, i32, i32, vp])
         _d(lib, f"bdx_flush_export_{suf}", [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp])
         _d(lib, f"bdx_fused_tables_{suf}", [i32, i32, vp, vp, vp])
@@ -92,6 +96,7 @@ def declare(lib) -> None:
     _d(lib, "bdx_rt_preflight", [vp, f64, vp])
     _d(lib, "bdx_rt_overlap_probe", [vp, i64, vp, i32, vp])
     _d(lib, "bdx_rt_bind_x", [vp, vp])
+    _d(lib, "bdx_rt_set_precond", [vp, vp, vp, vp, vp, vp, i32])
     _d(lib, "bdx_rt_wait", [vp])
     _d(lib, "bdx_rt_profile", [vp, ctypes.c_long, vp, i32])
     _d(lib, "bdx_rt_reset", [vp])

@@ -16,7 +16,10 @@ p0 = r0, rtol = 0 runs exactly max_iter iterations):
   host synchronisation (quirk Q3).
 
 When the operator provides `cg_start` / `cg_iterate` (the fused structured
-kernel, models/fused.py) the device loop delegates to it.
+kernel, models/fused.py) the device loop delegates to it.  The preconditioned
+solve does so only on request (`loop="fused"`): the fused kernels then run
+with u = z = dinv . r, r.z in the r.r slots, and an update pass that also
+stores z (csrc/hip/fused_common.hip).
 """
 
 from __future__ import annotations
@@ -88,9 +91,11 @@ class DeviceCG:
     """Device-resident CG state for the GPU platform.
 
     precond="jacobi": Jacobi-preconditioned CG with the problem's matrix-free
-    diagonal.  It always runs the generic loop (op.apply + dot + pcg_update +
-    pcg_p_update, z = dinv . r never stored), also for operators that offer a
-    fused `cg_start` / `cg_iterate`."""
+    diagonal.  loop="generic" (default) runs op.apply + dot + pcg_update +
+    pcg_p_update (z = dinv . r never stored), also for operators that offer a
+    fused `cg_start` / `cg_iterate`.  loop="fused" (precond="jacobi" only)
+    delegates to the operator's fused CG loop and its native runtime
+    (fused2/3/5); an operator without it raises ValueError in `start`."""
 
     # float64 scalar slots
     RR0, RR1, PAP = 0, 1, 2
@@ -98,10 +103,20 @@ class DeviceCG:
     # prologue's beta = 0 (slots 3, 4: the fused kernels' lagged alphas)
     RNORM, ZERO, ONE = 5, 6, 7
 
-    def __init__(self, pb, precond: str | None = None):
+    def __init__(self, pb, precond: str | None = None, loop: str = "generic"):
         if precond not in (None, "jacobi"):
             raise ValueError(f"unknown preconditioner {precond!r}")
+        if loop not in ("generic", "fused"):
+            raise ValueError(f"unknown loop {loop!r}")
+        if loop == "fused" and precond != "jacobi":
+            raise ValueError("loop='fused' selects the loop of the preconditioned solve: it "
+                             "needs precond='jacobi'")
+        self.loop = loop
         self.dinv = pb.jacobi_inverse() if precond == "jacobi" else None
+        # fused loop: z = dinv . r and the r.r block partials (allocated by
+        # the operator's cg_start)
+        self.z = None
+        self.partials_rr = None
         self.pb = pb
         self.k = pb.kernels
         dev = pb.device
@@ -111,7 +126,12 @@ class DeviceCG:
         self.partials = torch.zeros(self.k.npart, dtype=torch.float64, device=dev)
         self.r = pb.new_vector()
         self.y = pb.new_vector()
-        self.p = pb.new_vector()
+        # the fused loop keeps its search directions in the operator
+        self.p = pb.new_vector() if loop == "generic" else None
+
+    @property
+    def fused_pcg(self) -> bool:
+        return self.dinv is not None and self.loop == "fused"
 
     def _allreduce(self, slot: int) -> None:
         if self.pb.comm.size > 1:
@@ -121,6 +141,13 @@ class DeviceCG:
         """r0 = b - A x0, p0 = r0, rho0 = p0.r0 (the prologue of src/cg.hpp:98-112)."""
         self.op, self.x, self.it = op, x, 0
         k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
+        if self.fused_pcg:
+            if not getattr(op, "supports_fused_pcg", False):
+                name = getattr(op, "name", type(op).__name__)
+                raise ValueError(f"operator {name!r} has no fused preconditioned CG loop "
+                                 "(fused2, fused3 and fused5 do); use loop='generic'")
+            op.cg_start(self, x, b)
+            return
         if self.dinv is not None:
             # p0 = dinv . r0 (beta = 0 / 1), rz0 = p0.r0, rr0 = r0.r0
             op.apply(x, y)
@@ -147,6 +174,9 @@ class DeviceCG:
         last one pending for the next call (x is then one update behind)."""
         op, x = self.op, self.x
         k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
+        if self.fused_pcg:
+            op.cg_iterate(self, n, flush=flush)
+            return
         if self.dinv is not None:
             dinv = self.dinv
             for _ in range(n):
@@ -180,7 +210,7 @@ class DeviceCG:
         """iterate(n) plus the device time (ms) of each step.  The native
         runtime records timing events between its steps (same launches as
         iterate); the Python loop records torch events around each step."""
-        rt = getattr(self.op, "_rt", None) if self.dinv is None else None
+        rt = getattr(self.op, "_rt", None) if (self.dinv is None or self.fused_pcg) else None
         if rt is not None:
             return rt.iterate_timed(n)
         if self.pb.platform != "gpu":
@@ -200,7 +230,7 @@ class DeviceCG:
         """Host wait for the queued iterations.  With the native runtime the
         wait is bounded by the RCCL deadline (a hung peer raises instead of
         blocking torch.cuda.synchronize forever)."""
-        rt = getattr(self.op, "_rt", None) if self.dinv is None else None
+        rt = getattr(self.op, "_rt", None) if (self.dinv is None or self.fused_pcg) else None
         if rt is not None:
             rt.wait()
         elif self.pb.platform == "gpu":

@@ -249,6 +249,24 @@ class NativeCGRuntime:
             self.x = x
             self._keep[0] = x
 
+    def set_precond(self, dinv: torch.Tensor, z: torch.Tensor, partials_rr: torch.Tensor,
+                    rr_slot: int) -> None:
+        """Bind the Jacobi preconditioner (fused operators): the loop then
+        feeds the operator and the forward halo with z = dinv . r, stores z in
+        the update pass, keeps r.z in the r.r slots and the plain r.r in
+        scalar slot `rr_slot`.  z holds dinv . r0 when the iterations start
+        (FusedLaplacianGPU.cg_start).  Drops the captured graphs."""
+        if self.kind != "fused":
+            raise ValueError("the dofmap runtime has no preconditioned loop")
+        pb = self.pb
+        tb = [None, None]
+        if self.tiled:  # zeroed: the padding of the tiled z stays zero
+            n = pb.lat.tiled_size(self.op.sy, self.op.sz)
+            tb = [torch.zeros(n, dtype=pb.dtype, device=pb.device) for _ in range(2)]
+        self._keep += [dinv, z, partials_rr] + tb
+        _check(self.lib.bdx_rt_set_precond(self.h, ptr(dinv), ptr(z), ptr(tb[0]), ptr(tb[1]),
+                                           ptr(partials_rr), int(rr_slot)), "rt_set_precond")
+
     def reset(self) -> None:
         _check(self.lib.bdx_rt_reset(self.h), "rt_reset")
 
