@@ -11,8 +11,10 @@ Reference options (src/main.cpp:144-183): --platform, --float, --ndofs,
 
 MI355X extensions (additive): --kernel {auto,fused5,fused3,fused2,
 fused,v1,dofmap}, --geometry {auto,otf,otf-general,stored}, --kappa {constant,random},
---warmup N (untimed repetitions before the timed loop), --precond {none,jacobi}
-(with --cg: Jacobi-preconditioned CG with the matrix-free operator diagonal),
+--warmup N (untimed repetitions before the timed loop), --precond {none,jacobi,pmg}
+(with --cg: CG preconditioned with the matrix-free operator diagonal, or with
+a p-multigrid V-cycle; --pmg_smooth N / --pmg_coarse N: Chebyshev degree of
+its smoothers / of its degree-1 coarse solve),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -71,9 +73,14 @@ def build_parser() -> argparse.ArgumentParser:
                          "per-cell field U(1, 3) (partition-invariant)")
     ap.add_argument("--warmup", type=int, default=0,
                     help="Untimed repetitions before the timed loop")
-    ap.add_argument("--precond", default="none", choices=["none", "jacobi"],
+    ap.add_argument("--precond", default="none", choices=["none", "jacobi", "pmg"],
                     help="CG preconditioner (needs --cg): jacobi = the inverse of the "
-                         "matrix-free operator diagonal")
+                         "matrix-free operator diagonal; pmg = one p-multigrid V-cycle over "
+                         "the degrees P, P // 2, ..., 1 with Chebyshev-Jacobi smoothing")
+    ap.add_argument("--pmg_smooth", type=int, default=2,
+                    help="Chebyshev degree of the p-multigrid smoothers (--precond pmg)")
+    ap.add_argument("--pmg_coarse", type=int, default=8,
+                    help="Chebyshev degree of the p-multigrid degree-1 solve (--precond pmg)")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -92,6 +99,8 @@ def parse_args(argv=None):
         raise SystemExit("error: Invalid qmode.")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
+    if args.pmg_smooth < 1 or args.pmg_coarse < 1:
+        raise SystemExit("error: Options 'pmg_smooth' and 'pmg_coarse' must be positive")
     if args.pcg_loop == "fused" and not args.cg:
         raise SystemExit("error: Option 'pcg_loop fused' needs 'cg'")
     if args.pcg_loop == "fused" and args.precond != "jacobi":
@@ -189,7 +198,9 @@ def run_benchmark(comm, nx, args, platform):
                         platform, args.geom_perturb_fact, args.kappa)
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
-                         pcg_loop=args.pcg_loop)
+                         pcg_loop=args.pcg_loop,
+                         pmg_opts={"smooth_degree": args.pmg_smooth,
+                                   "coarse_degree": args.pmg_coarse})
     t = res.mat_free_time
     gdofs = pb.ndofs_global * args.nreps / (1e9 * t) if t > 0 else 0.0
     out = {"ncells_global": pb.ncells_global, "ndofs_global": pb.ndofs_global,

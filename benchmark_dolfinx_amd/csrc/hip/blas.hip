@@ -151,6 +151,34 @@ __global__ void __launch_bounds__(kBlock)
   }
 }
 
+// One step of the Chebyshev-Jacobi smoother (solvers/pmg.py) over the owned
+// rows, y = A z computed by the caller:  d = a d + b dinv (r - y);  z += d.
+// FIRST (the step from a zero guess):  d = b dinv r;  z = d, which reads
+// neither y nor the old d and z.  One pass of five reads and two writes.
+template <typename T, bool FIRST>
+__global__ void __launch_bounds__(kBlock)
+    cheb_step_kernel(RowSpace s, T a, T b, const T* __restrict__ dinv, const T* __restrict__ r,
+                     const T* __restrict__ y, T* __restrict__ d, T* __restrict__ z) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t nrows = s.o0 * s.o1;
+  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
+       row += static_cast<int64_t>(gridDim.x) * kWaves) {
+    const int64_t base = row_base(s, row);
+    for (int64_t k = lane; k < s.o2; k += 64) {
+      const int64_t i = base + k;
+      if constexpr (FIRST) {
+        const T dn = b * dinv[i] * r[i];
+        d[i] = dn;
+        z[i] = dn;
+      } else {
+        const T dn = a * d[i] + b * dinv[i] * (r[i] - y[i]);
+        d[i] = dn;
+        z[i] = z[i] + dn;
+      }
+    }
+  }
+}
+
 // out = alpha x + y over owned rows (reference axpy, src/vector.hpp:228-240).
 template <typename T>
 __global__ void __launch_bounds__(kBlock)
@@ -388,6 +416,22 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     pcg_p_update_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(        \
         s, p, r, dinv, scal, num, den);                                       \
+    return static_cast<int>(hipGetLastError());                               \
+  }                                                                           \
+  /* Chebyshev step: d = a d + b dinv (r - y); z += d (first: d = z = b */    \
+  /* dinv r; y may then be null) */                                           \
+  int bdx_cheb_step_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,     \
+                          int64_t o2, int first, double a, double b,          \
+                          const T* dinv, const T* r, const T* y, T* d, T* z,  \
+                          hipStream_t st) {                                   \
+    RowSpace s{L1, ld, o0, o1, o2};                                           \
+    const int g = grid_for_rows(o0 * o1);                                     \
+    if (first)                                                                \
+      cheb_step_kernel<T, true><<<g, kBlock, 0, st>>>(                        \
+          s, static_cast<T>(a), static_cast<T>(b), dinv, r, y, d, z);         \
+    else                                                                      \
+      cheb_step_kernel<T, false><<<g, kBlock, 0, st>>>(                       \
+          s, static_cast<T>(a), static_cast<T>(b), dinv, r, y, d, z);         \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
   int bdx_axpy_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,          \

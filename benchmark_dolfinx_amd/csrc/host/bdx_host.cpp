@@ -831,6 +831,141 @@ int64_t csr_build(const int64_t* latd, int nq, const T* B, const T* Dd,
   return nnz;
 }
 
+// ------------------------------------------------- p-multigrid transfers
+// Host twins of csrc/hip/lap_transfer.h: per cell P = J (x) J (x) J with
+// J (nf x nc, row-major) the coarse Lagrange basis at the fine nodes.
+inline bool transfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
+  if (lc.tsy || lf.tsy) return false;
+  if (lf.P < 2 || lf.P > 7 || lc.P != std::max<int64_t>(1, lf.P / 2)) return false;
+  for (int a = 0; a < 3; ++a) {
+    if (lc.n[a] != lf.n[a] || lc.n[a] < 0 || lc.gh[a] != lf.gh[a]) return false;
+    if (lc.L[a] != lc.n[a] * lc.P + 1 || lf.L[a] != lf.n[a] * lf.P + 1) return false;
+  }
+  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
+}
+
+// vf = P vc: every local fine node written once (a cell writes its local
+// indices < Pf, and Pf where it is the last local cell of the axis).
+template <typename T>
+int prolong_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vc,
+                 T* vf) {
+  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
+  if (!transfer_pair_ok(lc, lf)) return 1;
+  const int PF = static_cast<int>(lf.P), PC = static_cast<int>(lc.P), nf = PF + 1, nc = PC + 1;
+  T J[8 * 4];
+  for (int i = 0; i < nf * nc; ++i) J[i] = static_cast<T>(Jd[i]);
+  const int64_t n1 = lf.n[1], n2 = lf.n[2], ncell = lf.n[0] * n1 * n2;
+#pragma omp parallel for schedule(static)
+  for (int64_t cell = 0; cell < ncell; ++cell) {
+    const int64_t cz = cell % n2, cy = (cell / n2) % n1, cx = cell / (n1 * n2);
+    T s0[4 * 4 * 8], s1[4 * 8 * 8];
+    // z: (a, b, c) -> (a, b, k)
+    for (int a = 0; a < nc; ++a)
+      for (int b = 0; b < nc; ++b)
+        for (int k = 0; k < nf; ++k) {
+          T acc = 0;
+          for (int c = 0; c < nc; ++c)
+            acc += J[k * nc + c] * vc[lc.idx(cx * PC + a, cy * PC + b, cz * PC + c)];
+          s0[(a * nc + b) * nf + k] = acc;
+        }
+    // y: (a, b, k) -> (a, j, k)
+    for (int a = 0; a < nc; ++a)
+      for (int j = 0; j < nf; ++j)
+        for (int k = 0; k < nf; ++k) {
+          T acc = 0;
+          for (int b = 0; b < nc; ++b) acc += J[j * nc + b] * s0[(a * nc + b) * nf + k];
+          s1[(a * nf + j) * nf + k] = acc;
+        }
+    // x: (a, j, k) -> (i, j, k)
+    const int ex = cx == lf.n[0] - 1 ? nf : PF, ey = cy == n1 - 1 ? nf : PF,
+              ez = cz == n2 - 1 ? nf : PF;
+    for (int i = 0; i < ex; ++i)
+      for (int j = 0; j < ey; ++j)
+        for (int k = 0; k < ez; ++k) {
+          T acc = 0;
+          for (int a = 0; a < nc; ++a) acc += J[i * nc + a] * s1[(a * nf + j) * nf + k];
+          vf[lf.idx(cx * PF + i, cy * PF + j, cz * PF + k)] = acc;
+        }
+  }
+  return 0;
+}
+
+// vc += P^T vf: each cell takes the fine nodes prolong_host writes, owned ones
+// only; cells of one parity colour share no coarse dof, so the colours run
+// one after the other (fixed order) and each in parallel.
+template <typename T>
+int restrict_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vf,
+                  T* vc) {
+  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
+  if (!transfer_pair_ok(lc, lf)) return 1;
+  const int PF = static_cast<int>(lf.P), PC = static_cast<int>(lc.P), nf = PF + 1, nc = PC + 1;
+  T J[8 * 4];
+  for (int i = 0; i < nf * nc; ++i) J[i] = static_cast<T>(Jd[i]);
+  for (int colour = 0; colour < 8; ++colour) {
+    const int64_t o[3] = {(colour >> 2) & 1, (colour >> 1) & 1, colour & 1};
+    int64_t e[3];
+    for (int a = 0; a < 3; ++a) e[a] = lf.n[a] > o[a] ? (lf.n[a] - o[a] + 1) / 2 : 0;
+    const int64_t ncell = e[0] * e[1] * e[2];
+#pragma omp parallel for schedule(static)
+    for (int64_t cell = 0; cell < ncell; ++cell) {
+      const int64_t cz = o[2] + 2 * (cell % e[2]), cy = o[1] + 2 * ((cell / e[2]) % e[1]),
+                    cx = o[0] + 2 * (cell / (e[1] * e[2]));
+      T s0[4 * 8 * 8], s1[4 * 4 * 8];
+      const int ex = cx == lf.n[0] - 1 ? nf : PF, ey = cy == lf.n[1] - 1 ? nf : PF,
+                ez = cz == lf.n[2] - 1 ? nf : PF;
+      // x: (i, j, k) -> (a, j, k)
+      for (int a = 0; a < nc; ++a)
+        for (int j = 0; j < nf; ++j)
+          for (int k = 0; k < nf; ++k) {
+            T acc = 0;
+            if (j < ey && k < ez)
+              for (int i = 0; i < ex; ++i) {
+                const int64_t li = cx * PF + i, lj = cy * PF + j, lk = cz * PF + k;
+                if (lf.is_owned(li, lj, lk)) acc += J[i * nc + a] * vf[lf.idx(li, lj, lk)];
+              }
+            s0[(a * nf + j) * nf + k] = acc;
+          }
+      // y: (a, j, k) -> (a, b, k)
+      for (int a = 0; a < nc; ++a)
+        for (int b = 0; b < nc; ++b)
+          for (int k = 0; k < nf; ++k) {
+            T acc = 0;
+            for (int j = 0; j < nf; ++j) acc += J[j * nc + b] * s0[(a * nf + j) * nf + k];
+            s1[(a * nc + b) * nf + k] = acc;
+          }
+      // z: (a, b, k) -> (a, b, c)
+      for (int a = 0; a < nc; ++a)
+        for (int b = 0; b < nc; ++b)
+          for (int c = 0; c < nc; ++c) {
+            T acc = 0;
+            for (int k = 0; k < nf; ++k) acc += J[k * nc + c] * s1[(a * nc + b) * nf + k];
+            vc[lc.idx(cx * PC + a, cy * PC + b, cz * PC + c)] += acc;
+          }
+    }
+  }
+  return 0;
+}
+
+// Host twin of bdx_cheb_step (csrc/hip/blas.hip) over the owned rows.
+template <typename T>
+void cheb_step_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, int first, T a,
+                    T b, const T* dinv, const T* r, const T* y, T* d, T* z) {
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t i = 0; i < o0; ++i)
+    for (int64_t j = 0; j < o1; ++j) {
+      const int64_t base = (i * L1 + j) * ld;
+      for (int64_t k = base; k < base + o2; ++k) {
+        if (first) {
+          d[k] = b * dinv[k] * r[k];
+          z[k] = d[k];
+        } else {
+          d[k] = a * d[k] + b * dinv[k] * (r[k] - y[k]);
+          z[k] = z[k] + d[k];
+        }
+      }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -942,6 +1077,26 @@ int bdx_host_version() { return 1; }
       a.hi[c] = hi[c];                                                        \
     }                                                                         \
     dispatch<Diag<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
+  }                                                                           \
+  /* p-multigrid transfers between the coarse and fine lattices latc / latf */ \
+  /* (J: the (Pf + 1) x (Pc + 1) 1D table): vf = P vc, vc += P^T vf; the   */ \
+  /* host twins of bdx_prolong / bdx_restrict, nonzero for a bad pair      */ \
+  int bdx_cpu_prolong_##SUF(const int64_t* latc, const int64_t* latf,         \
+                            const double* J, const T* vc, T* vf) {            \
+    return prolong_host<T>(latc, latf, J, vc, vf);                            \
+  }                                                                           \
+  int bdx_cpu_restrict_##SUF(const int64_t* latc, const int64_t* latf,        \
+                             const double* J, const T* vf, T* vc) {           \
+    return restrict_host<T>(latc, latf, J, vf, vc);                           \
+  }                                                                           \
+  /* Chebyshev step d = a d + b dinv (r - y); z += d (first: d = z = b dinv */ \
+  /* r), the host twin of bdx_cheb_step                                    */ \
+  void bdx_cpu_cheb_step_##SUF(int64_t L1, int64_t ld, int64_t o0,            \
+                               int64_t o1, int64_t o2, int first, double a,   \
+                               double b, const T* dinv, const T* r,           \
+                               const T* y, T* d, T* z) {                      \
+    cheb_step_host<T>(L1, ld, o0, o1, o2, first, static_cast<T>(a),           \
+                      static_cast<T>(b), dinv, r, y, d, z);                   \
   }                                                                           \
   int64_t bdx_cpu_csr_##SUF(const int64_t* latd, int nq, const T* B,          \
                             const T* Dd, const T* wts, const T* qpts,         \

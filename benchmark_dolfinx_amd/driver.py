@@ -109,13 +109,14 @@ def _sync(pb: PoissonProblem) -> None:
         torch.cuda.synchronize()
 
 
-def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg, dinv=None):
+def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg, dinv=None, pmg=None):
     if use_cg:
         if pb.platform == "gpu":
             dev_cg.solve(op, x, u, nreps)
             dev_cg.wait()  # bounded by the RCCL deadline (native runtime)
         else:
-            cg_solve(op, pb, x, u, nreps, 0.0, dinv=dinv)
+            cg_solve(op, pb, x, u, nreps, 0.0, dinv=dinv,
+                     precond=None if pmg is None else pmg.apply)
     else:
         for _ in range(nreps):
             op.apply(u, x)
@@ -124,14 +125,18 @@ def _run_loop(op, pb, x, u, nreps, use_cg, dev_cg, dinv=None):
 def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
                    kernel: str = "auto", geometry: str = "auto", warmup: int = 0,
                    printer=print, precond: str = "none",
-                   pcg_loop: str = "generic") -> BenchmarkResults:
+                   pcg_loop: str = "generic", pmg_opts: dict | None = None) -> BenchmarkResults:
     """precond="jacobi" (CG only): Jacobi-preconditioned CG with the
     matrix-free diagonal; the CSR comparison solve is then preconditioned
     with the diagonal read off the assembled matrix, so the error norm
     cross-checks the two diagonals end to end.  pcg_loop="fused" (GPU,
     precond="jacobi"): the preconditioned solve runs the fused operator's CG
-    fusion and native runtime instead of the generic device loop."""
-    if precond not in ("none", "jacobi"):
+    fusion and native runtime instead of the generic device loop.
+    precond="pmg" (CG only): a p-multigrid V-cycle (solvers/pmg.py; `pmg_opts`:
+    keyword arguments of `PMultigrid`); the CSR comparison solve is
+    preconditioned with the same `PMultigrid` object, so the error norm
+    again compares two solves with one algorithm."""
+    if precond not in ("none", "jacobi", "pmg"):
         raise ValueError(f"unknown preconditioner {precond!r}")
     if precond != "none" and not use_cg:
         raise ValueError("a preconditioner needs the CG solve (use_cg)")
@@ -150,23 +155,33 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
         op = make_operator(pb, kernel, geometry)
         if pb.platform == "gpu":
             torch.cuda.synchronize()
+    pmg = None
+    if precond == "pmg":
+        from .solvers.pmg import PMultigrid
+        with timed("~setup p-multigrid"):
+            pmg = PMultigrid(pb, **(pmg_opts or {}))
     dev_cg = None
     if use_cg and pb.platform == "gpu":
-        dev_cg = DeviceCG(pb, "jacobi", loop=pcg_loop) if jacobi else DeviceCG(pb)
+        if pmg is not None:
+            dev_cg = DeviceCG(pb, "pmg", pmg=pmg)
+        else:
+            dev_cg = DeviceCG(pb, "jacobi", loop=pcg_loop) if jacobi else DeviceCG(pb)
     dinv = pb.jacobi_inverse() if jacobi else None
     res.extra["kernel"] = getattr(op, "name", type(op).__name__)
     res.extra["geometry"] = getattr(op, "geometry", "otf")
-    if jacobi:  # the default run's JSON stays exactly what it was
+    if precond != "none":  # the default run's JSON stays exactly what it was
         res.extra["precond"] = precond
+    if pmg is not None:
+        res.extra["pmg"] = pmg.info()
     if pcg_loop != "generic":  # only when the option is used
         res.extra["pcg_loop"] = pcg_loop
     if warmup > 0:
         with timed("~warmup"):
-            _run_loop(op, pb, y, u, warmup, use_cg, dev_cg, dinv)
+            _run_loop(op, pb, y, u, warmup, use_cg, dev_cg, dinv, pmg)
             y.zero_()
     _sync(pb)
     t0 = time.perf_counter()
-    _run_loop(op, pb, y, u, nreps, use_cg, dev_cg, dinv)
+    _run_loop(op, pb, y, u, nreps, use_cg, dev_cg, dinv, pmg)
     _sync(pb)
     dt = time.perf_counter() - t0
     dt = pb.comm.allreduce_scalar(dt, "max")
@@ -189,7 +204,8 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
         _sync(pb)
         with timed("% CSR Matvec", sync=lambda: _sync(pb)):
             if use_cg:
-                cg_solve(A, pb, z, u, nreps, 0.0, dinv=dinv_csr)
+                cg_solve(A, pb, z, u, nreps, 0.0, dinv=dinv_csr,
+                         precond=None if pmg is None else pmg.apply)
             else:
                 for _ in range(nreps):
                     A.apply(u, z)
@@ -202,6 +218,8 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
             printer(f"Norm of error = {res.enorm:.6g}")
             rel = res.enorm / res.znorm if res.znorm != 0 else float("nan")
             printer(f"Relative norm of error = {rel:.6g}")
+    if pmg is not None:
+        pmg.close()
     if hasattr(op, "close"):
         op.close()  # native runtime: release RCCL / graphs before shutdown
     return res

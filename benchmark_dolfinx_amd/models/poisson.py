@@ -102,6 +102,7 @@ class PoissonProblem:
         self.degree = degree
         self.qmode = qmode
         self.use_gauss = use_gauss
+        self.perturb, self.shear = perturb, shear  # kept for the p-multigrid levels
         self.tables = OperatorTables(degree, qmode, use_gauss)
         # "yz": keep the march axis x whole (halo/compute overlap of the fused
         # GPU runtime); "xyz": minimum cut area.  Default: yz on the GPU.

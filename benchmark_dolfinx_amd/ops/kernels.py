@@ -185,6 +185,27 @@ class HipKernels:
         _check(self._f("bdx_axpy")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], ptr(out),
                                    float(alpha), ptr(x), ptr(y), _stream()), "axpy")
 
+    # --------------------------------------------------------- p-multigrid
+    def cheb_step(self, first: bool, a: float, b: float, dinv, r, y, d, z):
+        """d = a d + b dinv (r - y); z += d over the owned rows (first: d = z =
+        b dinv r, y unused)."""
+        L = self.lat
+        _check(self._f("bdx_cheb_step")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], int(first),
+                                        float(a), float(b), ptr(dinv), ptr(r), ptr(y), ptr(d),
+                                        ptr(z), _stream()), "cheb_step")
+
+    def prolong(self, latd_c, J, vc, vf):
+        """vf = P vc from the coarse lattice `latd_c` to this (fine) lattice;
+        J: the (Pf + 1) x (Pc + 1) float64 table (lap_transfer.h)."""
+        _check(self._f("bdx_prolong")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vc), ptr(vf),
+                                      _stream()), "prolong")
+
+    def restrict(self, latd_c, J, vf, vc):
+        """vc += P^T vf (owned fine dofs; vc zeroed by the caller; eight colour
+        launches in a fixed order, no atomics)."""
+        _check(self._f("bdx_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc),
+                                       _stream()), "restrict")
+
     def box_copy(self, mode: int, vec, lat, side, buf):
         _check(self._f("bdx_box_copy")(mode, ptr(vec), lat.L[1], lat.ld, ptr(side.table),
                                        len(side.boxes), side.total, ptr(buf), _stream()),
@@ -194,6 +215,39 @@ class HipKernels:
         """y[r] (+)= sum of vals[p] x[cols[p]] over p in [beg[r], end[r])."""
         _check(self._f("bdx_spmv")(nrows, ptr(beg), ptr(end), ptr(cols), ptr(vals), ptr(x),
                                    ptr(y), int(acc), _stream()), "spmv")
+
+
+class HostKernels:
+    """The p-multigrid kernels of `HipKernels` on the host twins
+    (csrc/host/bdx_host.cpp), so the CPU platform runs the same Python path."""
+
+    def __init__(self, lat, dtype):
+        self.lib = native.host()
+        self.lat = lat
+        self.latd = lat.as_int64()
+        self.suf = _suf(dtype)
+        self.o = lat.owned_hi
+
+    def _f(self, name):
+        return getattr(self.lib, f"{name}_{self.suf}")
+
+    def cheb_step(self, first: bool, a: float, b: float, dinv, r, y, d, z):
+        L = self.lat
+        self._f("bdx_cpu_cheb_step")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], int(first),
+                                     float(a), float(b), ptr(dinv), ptr(r), ptr(y), ptr(d), ptr(z))
+
+    def prolong(self, latd_c, J, vc, vf):
+        if self._f("bdx_cpu_prolong")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vc), ptr(vf)):
+            raise ValueError("prolong: lattice pair outside the p-multigrid schedule")
+
+    def restrict(self, latd_c, J, vf, vc):
+        if self._f("bdx_cpu_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc)):
+            raise ValueError("restrict: lattice pair outside the p-multigrid schedule")
+
+    def axpy(self, out, alpha: float, x, y):
+        o = self.o
+        sl = (slice(0, o[0]), slice(0, o[1]), slice(0, o[2]))
+        torch.add(y[sl], x[sl], alpha=float(alpha), out=out[sl])
 
 
 def device_info(dev: int = 0) -> str:

@@ -80,6 +80,10 @@ def host():
                          [vp, i32, vp, vp, vp, vp, vp, ft, vp, vp, vp, vp, i32], i64)
                 _declare(lib, f"bdx_cpu_spmv_{suf}", [i64, vp, vp, vp, vp, vp, vp, i32])
                 _declare(lib, f"bdx_cpu_interp_f_{suf}", [vp, vp, vp, vp])
+                _declare(lib, f"bdx_cpu_prolong_{suf}", [vp, vp, vp, vp, vp], i32)
+                _declare(lib, f"bdx_cpu_restrict_{suf}", [vp, vp, vp, vp, vp], i32)
+                _declare(lib, f"bdx_cpu_cheb_step_{suf}",
+                         [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
             _host = lib
     return _host
 

@@ -1,6 +1,9 @@
 """Conjugate gradients (reference: `cg_solve`, src/cg.hpp:89-169), unpreconditioned
 by default, optionally Jacobi-preconditioned with the matrix-free diagonal
-(`cg_solve(..., dinv=...)`, `DeviceCG(pb, precond="jacobi")`).
+(`cg_solve(..., dinv=...)`, `DeviceCG(pb, precond="jacobi")`) or with any
+symmetric positive definite M^-1 given as a callable (`cg_solve(...,
+precond=...)`), such as the p-multigrid V-cycle of solvers/pmg.py
+(`DeviceCG(pb, precond="pmg")`).
 
 Two implementations with the reference's algorithm (x0 given, r0 = b - A x0,
 p0 = r0, rtol = 0 runs exactly max_iter iterations):
@@ -28,11 +31,17 @@ import torch
 
 
 def cg_solve(op, pb, x: torch.Tensor, b: torch.Tensor, max_iter: int,
-             rtol: float = 0.0, dinv: torch.Tensor | None = None) -> int:
+             rtol: float = 0.0, dinv: torch.Tensor | None = None, precond=None) -> int:
     """`dinv` (lattice-shaped 1 / diag(A), `PoissonProblem.jacobi_inverse`):
-    Jacobi-preconditioned CG; None: the unpreconditioned algorithm."""
+    Jacobi-preconditioned CG; `precond`: a callable `precond(r, z)` that
+    writes z = M^-1 r (e.g. `PMultigrid.apply`); neither: the unpreconditioned
+    algorithm."""
+    if dinv is not None and precond is not None:
+        raise ValueError("give dinv or precond, not both")
     if dinv is not None:
         return _pcg_solve(op, pb, x, b, max_iter, rtol, dinv)
+    if precond is not None:
+        return _pcg_solve_callable(op, pb, x, b, max_iter, rtol, precond)
     r = pb.new_vector()
     y = pb.new_vector()
     op.apply(x, y)
@@ -87,6 +96,36 @@ def _pcg_solve(op, pb, x, b, max_iter: int, rtol: float, dinv) -> int:
     return k
 
 
+def _pcg_solve_callable(op, pb, x, b, max_iter: int, rtol: float, precond) -> int:
+    """PCG with z = M^-1 r computed by `precond(r, z)`; same recurrence and
+    stop test as `_pcg_solve`."""
+    r = pb.new_vector()
+    y = pb.new_vector()
+    z = pb.new_vector()
+    op.apply(x, y)
+    r.copy_(b - y)
+    precond(r, z)
+    p = z.clone()
+    rz = pb.inner(r, z)
+    rtol2 = rtol * rtol
+    rnorm0 = pb.inner(r, r) if rtol2 > 0 else 0.0
+    k = 0
+    while k < max_iter:
+        k += 1
+        op.apply(p, y)
+        alpha = rz / pb.inner(p, y)
+        x.add_(p, alpha=alpha)
+        r.add_(y, alpha=-alpha)
+        precond(r, z)
+        rz_new = pb.inner(r, z)
+        beta = rz_new / rz
+        rz = rz_new
+        if rnorm0 > 0 and pb.inner(r, r) / rnorm0 < rtol2:
+            break
+        p.mul_(beta).add_(z)
+    return k
+
+
 class DeviceCG:
     """Device-resident CG state for the GPU platform.
 
@@ -95,7 +134,12 @@ class DeviceCG:
     pcg_p_update (z = dinv . r never stored), also for operators that offer a
     fused `cg_start` / `cg_iterate`.  loop="fused" (precond="jacobi" only)
     delegates to the operator's fused CG loop and its native runtime
-    (fused2/3/5); an operator without it raises ValueError in `start`."""
+    (fused2/3/5); an operator without it raises ValueError in `start`.
+
+    precond="pmg": CG preconditioned with a p-multigrid V-cycle (`pmg`: a
+    `PMultigrid` of the problem; None builds the default one).  Generic loop
+    only, composed of existing kernels: op.apply, dot, cg_update (r.r into
+    RNORM), `pmg.apply(r, z)` with z stored here, dot(r, z), p_update."""
 
     # float64 scalar slots
     RR0, RR1, PAP = 0, 1, 2
@@ -103,16 +147,22 @@ class DeviceCG:
     # prologue's beta = 0 (slots 3, 4: the fused kernels' lagged alphas)
     RNORM, ZERO, ONE = 5, 6, 7
 
-    def __init__(self, pb, precond: str | None = None, loop: str = "generic"):
-        if precond not in (None, "jacobi"):
+    def __init__(self, pb, precond: str | None = None, loop: str = "generic", pmg=None):
+        if precond not in (None, "jacobi", "pmg"):
             raise ValueError(f"unknown preconditioner {precond!r}")
         if loop not in ("generic", "fused"):
             raise ValueError(f"unknown loop {loop!r}")
         if loop == "fused" and precond != "jacobi":
             raise ValueError("loop='fused' selects the loop of the preconditioned solve: it "
                              "needs precond='jacobi'")
+        if pmg is not None and precond != "pmg":
+            raise ValueError("pmg= needs precond='pmg'")
         self.loop = loop
         self.dinv = pb.jacobi_inverse() if precond == "jacobi" else None
+        self.pmg = None
+        if precond == "pmg":
+            from .pmg import PMultigrid
+            self.pmg = pmg if pmg is not None else PMultigrid(pb)
         # fused loop: z = dinv . r and the r.r block partials (allocated by
         # the operator's cg_start)
         self.z = None
@@ -126,12 +176,19 @@ class DeviceCG:
         self.partials = torch.zeros(self.k.npart, dtype=torch.float64, device=dev)
         self.r = pb.new_vector()
         self.y = pb.new_vector()
+        if self.pmg is not None:
+            self.z = pb.new_vector()
         # the fused loop keeps its search directions in the operator
         self.p = pb.new_vector() if loop == "generic" else None
 
     @property
     def fused_pcg(self) -> bool:
         return self.dinv is not None and self.loop == "fused"
+
+    @property
+    def _op_drives_loop(self) -> bool:
+        """The operator's own CG loop (and native runtime) runs the solve."""
+        return self.pmg is None and (self.dinv is None or self.fused_pcg)
 
     def _allreduce(self, slot: int) -> None:
         if self.pb.comm.size > 1:
@@ -147,6 +204,18 @@ class DeviceCG:
                 raise ValueError(f"operator {name!r} has no fused preconditioned CG loop "
                                  "(fused2, fused3 and fused5 do); use loop='generic'")
             op.cg_start(self, x, b)
+            return
+        if self.pmg is not None:
+            # r0 = b - A x0, z0 = M^-1 r0, p0 = z0, rz0 = r0.z0, rr0 = r0.r0
+            z = self.z
+            op.apply(x, y)
+            k.axpy(r, -1.0, y, b)
+            self.pmg.apply(r, z)
+            p.copy_(z)
+            k.dot(r, z, self.partials, scal, self.RR0)
+            self._allreduce(self.RR0)
+            k.dot(r, r, self.partials, scal, self.RNORM)
+            self._allreduce(self.RNORM)
             return
         if self.dinv is not None:
             # p0 = dinv . r0 (beta = 0 / 1), rz0 = p0.r0, rr0 = r0.r0
@@ -176,6 +245,22 @@ class DeviceCG:
         k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
         if self.fused_pcg:
             op.cg_iterate(self, n, flush=flush)
+            return
+        if self.pmg is not None:
+            z = self.z
+            for _ in range(n):
+                cur = self.RR0 if self.it % 2 == 0 else self.RR1
+                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
+                op.apply(p, y)
+                k.dot(p, y, self.partials, scal, self.PAP)
+                self._allreduce(self.PAP)
+                k.cg_update(x, r, p, y, scal, cur, self.PAP, self.RNORM, self.partials)
+                self._allreduce(self.RNORM)
+                self.pmg.apply(r, z)
+                k.dot(r, z, self.partials, scal, nxt)
+                self._allreduce(nxt)
+                k.p_update(p, z, scal, nxt, cur)
+                self.it += 1
             return
         if self.dinv is not None:
             dinv = self.dinv
@@ -210,7 +295,7 @@ class DeviceCG:
         """iterate(n) plus the device time (ms) of each step.  The native
         runtime records timing events between its steps (same launches as
         iterate); the Python loop records torch events around each step."""
-        rt = getattr(self.op, "_rt", None) if (self.dinv is None or self.fused_pcg) else None
+        rt = getattr(self.op, "_rt", None) if self._op_drives_loop else None
         if rt is not None:
             return rt.iterate_timed(n)
         if self.pb.platform != "gpu":
@@ -230,7 +315,7 @@ class DeviceCG:
         """Host wait for the queued iterations.  With the native runtime the
         wait is bounded by the RCCL deadline (a hung peer raises instead of
         blocking torch.cuda.synchronize forever)."""
-        rt = getattr(self.op, "_rt", None) if (self.dinv is None or self.fused_pcg) else None
+        rt = getattr(self.op, "_rt", None) if self._op_drives_loop else None
         if rt is not None:
             rt.wait()
         elif self.pb.platform == "gpu":
@@ -242,7 +327,7 @@ class DeviceCG:
         return max_iter
 
     def residual_norm2(self) -> float:
-        if self.dinv is not None:
+        if self.dinv is not None or self.pmg is not None:
             return float(self.scal[self.RNORM].item())
         slot = self.RR0 if self.it % 2 == 0 else self.RR1
         return float(self.scal[slot].item())

@@ -1,0 +1,204 @@
+"""p-multigrid preconditioner: one V-cycle over the degrees P, max(1, P // 2),
+..., 1 on the same cells, with Chebyshev-Jacobi smoothing on every level.
+
+Every level is a `PoissonProblem` of its degree on the same cells, partition,
+perturbation and per-cell kappa; its operator comes from `make_operator`, its
+smoothing diagonal from `jacobi_inverse()`.  The transfers are the nodal
+interpolation J (x) J (x) J per cell (J[a, i] = l_i^c(xi_a^f), the coarse GLL
+Lagrange basis at the fine GLL nodes) and its exact transpose
+(csrc/hip/lap_transfer.h, host twins in csrc/host/bdx_host.cpp).
+
+V-cycle on level l with residual r:
+    z = smooth(r, zero guess);  res = r - A z;  r_c = R res;
+    z += P Vcycle(l + 1, r_c);  z = smooth(r, z)
+with the same polynomial before and after, so M^-1 is symmetric and plain PCG
+applies.  The coarsest level (degree 1) is the same Chebyshev iteration from a
+zero guess with a higher degree and a wider interval.
+
+Chebyshev-Jacobi of degree k on [lhi / range, lhi], lhi = 1.1 x the estimate
+of lambda_max(D^-1 A) from `eig_iters` power iterations: with theta = (lhi +
+llo) / 2, delta = (lhi - llo) / 2, sigma = theta / delta, rho_0 = 1 / sigma
+    d = (1 / theta) D^-1 res;  z += d
+    rho' = 1 / (2 sigma - rho);  d = rho' rho d + (2 rho' / delta) D^-1 (r - A z);  z += d
+All coefficients are host doubles fixed at setup, so a cycle runs without any
+host synchronisation: operator applies, one fused vector kernel per Chebyshev
+step (`cheb_step`), axpy, the two transfer kernels and the halo exchanges.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from ..fem.mesh import _hash_uniform
+from ..fem.quadrature import lagrange_tables
+from ..models.poisson import PoissonProblem
+
+
+def level_degrees(P: int) -> list[int]:
+    """P, max(1, P // 2), ... down to 1 (7-3-1, 6-3-1, 5-2-1, 4-2-1, 3-1, 2-1, 1)."""
+    out = [int(P)]
+    while out[-1] > 1:
+        out.append(max(1, out[-1] // 2))
+    return out
+
+
+def chebyshev_coefficients(lam_hi: float, rng: float, degree: int) -> list[tuple[float, float]]:
+    """(a, b) of every step d = a d + b D^-1 res of the degree-`degree`
+    Chebyshev iteration on [lam_hi / rng, lam_hi]; the first has a = 0."""
+    lo = lam_hi / rng
+    theta, delta = 0.5 * (lam_hi + lo), 0.5 * (lam_hi - lo)
+    sigma = theta / delta
+    rho = 1.0 / sigma
+    out = [(0.0, 1.0 / theta)]
+    for _ in range(degree - 1):
+        rho_new = 1.0 / (2.0 * sigma - rho)
+        out.append((rho_new * rho, 2.0 * rho_new / delta))
+        rho = rho_new
+    return out
+
+
+class _Level:
+    """One degree of the hierarchy: problem, operator, smoother data, work vectors."""
+
+    def __init__(self, pb: PoissonProblem):
+        from ..driver import make_operator  # driver imports solvers.cg: import lazily
+        from ..ops.kernels import HostKernels
+        self.pb = pb
+        self.op = make_operator(pb, "auto", "auto")
+        self.k = pb.kernels if pb.kernels is not None else HostKernels(pb.lat, pb.dtype)
+        self.dinv = pb.jacobi_inverse()
+        self.bc = pb.bc_mask()
+        self.latd = pb.lat.as_int64()
+        self.y = pb.new_vector()    # A z
+        self.d = pb.new_vector()    # Chebyshev direction
+        self.t = pb.new_vector()    # residual, then the prolonged correction
+        self.r = None               # coarse levels: the restricted residual
+        self.z = None               # coarse levels: the correction
+        self.J = None               # table to the next coarser level
+        self.coef = []
+        self.lambda_max = 0.0
+
+
+class PMultigrid:
+    """z = M^-1 r by one p-multigrid V-cycle (module docstring).
+
+    degrees: the level degrees; lambda_max: the estimate of lambda_max(D^-1 A)
+    per level (the smoothers' upper bound is 1.1 x it)."""
+
+    def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
+                 coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10):
+        if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
+            raise ValueError("smoother degrees and eig_iters must be positive")
+        if smooth_range <= 1.0 or coarse_range <= 1.0:
+            raise ValueError("smoother ranges must exceed 1")
+        self.pb = pb
+        self.smooth_degree, self.smooth_range = int(smooth_degree), float(smooth_range)
+        self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
+        self.degrees = level_degrees(pb.degree)
+        self.levels: list[_Level] = []
+        ncells = pb.lat.ncells_global
+        for i, P in enumerate(self.degrees):
+            lpb = pb if i == 0 else PoissonProblem(
+                pb.comm, ncells, P, pb.qmode, pb.use_gauss, pb.dtype, pb.platform,
+                pb.perturb, pb.coefficient, shear=pb.shear, partition=pb.partition)
+            lv = _Level(lpb)
+            if i > 0:
+                lv.r, lv.z = lpb.new_vector(), lpb.new_vector()
+            self.levels.append(lv)
+        for i, lv in enumerate(self.levels):
+            coarsest = i == len(self.levels) - 1
+            if not coarsest:
+                nxt = self.levels[i + 1].pb
+                J, _ = lagrange_tables(nxt.tables.nodes, lv.pb.tables.nodes)
+                lv.J = np.ascontiguousarray(J, dtype=np.float64)
+            lv.lambda_max = self._power_iteration(lv, eig_iters)
+            if coarsest:
+                lv.coef = chebyshev_coefficients(1.1 * lv.lambda_max, self.coarse_range,
+                                                 self.coarse_degree)
+            else:
+                lv.coef = chebyshev_coefficients(1.1 * lv.lambda_max, self.smooth_range,
+                                                 self.smooth_degree)
+        self.lambda_max = [lv.lambda_max for lv in self.levels]
+
+    # ---------------------------------------------------------------- setup
+    @staticmethod
+    def _power_iteration(lv: _Level, iters: int) -> float:
+        """Rayleigh quotient <v, D^-1 A v>, |v| = 1, after `iters` power
+        iterations from a start vector hashed from the global lexicographic
+        dof index (the same for every partition), zero on Dirichlet dofs."""
+        pb = lv.pb
+        v0 = np.zeros(pb.lat.shape, dtype=np.float64)
+        gid = pb.lat.global_indices().astype(np.uint64)
+        v0[:, :, : pb.lat.L[2]] = np.where(pb.lat.bc_mask(), 0.0, 2.0 * _hash_uniform(gid, 11) - 1.0)
+        v = torch.from_numpy(v0).to(pb.device, pb.dtype)
+        w = pb.new_vector()
+        lam = 0.0
+        for _ in range(iters):
+            nrm = pb.norm(v)
+            if not nrm > 0.0:
+                return 1.0  # no interior dof: D^-1 A is the identity
+            pb.scale(v, 1.0 / nrm)
+            lv.op.apply(v, lv.y)
+            pb.pointwise_mult(w, lv.dinv, lv.y)
+            lam = pb.inner(v, w)
+            pb.copy(v, w)
+        return float(lam)
+
+    # ------------------------------------------------------------ transfers
+    def prolong(self, l: int, vc: torch.Tensor, vf: torch.Tensor) -> None:
+        """vf = P vc from level l + 1 to level l (every local fine node; the
+        coarse ghost planes are read, so vc is forward-exchanged first)."""
+        fine, coarse = self.levels[l], self.levels[l + 1]
+        coarse.pb.halo.forward(vc)
+        fine.k.prolong(coarse.latd, fine.J, vc, vf)
+
+    def restrict(self, l: int, vf: torch.Tensor, vc: torch.Tensor) -> None:
+        """vc = P^T vf from level l to level l + 1: owned fine dofs only, the
+        partial sums on the coarse ghost planes reverse-exchanged to their
+        owners, Dirichlet entries zeroed, then forwarded to the ghosts."""
+        fine, coarse = self.levels[l], self.levels[l + 1]
+        vc.zero_()
+        fine.k.restrict(coarse.latd, fine.J, vf, vc)
+        coarse.pb.halo.reverse(vc)
+        vc.masked_fill_(coarse.bc, 0.0)
+        coarse.pb.halo.forward(vc)
+
+    # ---------------------------------------------------------------- cycle
+    @staticmethod
+    def _smooth(lv: _Level, r: torch.Tensor, z: torch.Tensor, zero_guess: bool) -> None:
+        for i, (a, b) in enumerate(lv.coef):
+            if i == 0 and zero_guess:
+                lv.k.cheb_step(True, 0.0, b, lv.dinv, r, None, lv.d, z)
+            else:
+                lv.op.apply(z, lv.y)
+                lv.k.cheb_step(False, a, b, lv.dinv, r, lv.y, lv.d, z)
+
+    def _vcycle(self, l: int, r: torch.Tensor, z: torch.Tensor) -> None:
+        lv = self.levels[l]
+        self._smooth(lv, r, z, True)
+        if l == len(self.levels) - 1:
+            return
+        nxt = self.levels[l + 1]
+        lv.op.apply(z, lv.y)
+        lv.k.axpy(lv.t, -1.0, lv.y, r)          # res = r - A z
+        self.restrict(l, lv.t, nxt.r)
+        self._vcycle(l + 1, nxt.r, nxt.z)
+        self.prolong(l, nxt.z, lv.t)
+        lv.k.axpy(z, 1.0, lv.t, z)              # z += P z_c
+        self._smooth(lv, r, z, False)
+
+    def apply(self, r: torch.Tensor, z: torch.Tensor) -> None:
+        """z = M^-1 r (lattice-shaped; the owned entries are valid).  r is not
+        modified; it must vanish on Dirichlet dofs, as every CG residual does."""
+        self._vcycle(0, r, z)
+
+    def info(self) -> dict:
+        return {"degrees": list(self.degrees), "lambda_max": list(self.lambda_max),
+                "smooth_degree": self.smooth_degree, "coarse_degree": self.coarse_degree}
+
+    def close(self) -> None:
+        """Close the level operators (native runtimes, if any was started)."""
+        for lv in self.levels:
+            if hasattr(lv.op, "close"):
+                lv.op.close()

@@ -1,0 +1,198 @@
+#!/usr/bin/env python3
+"""p-multigrid preconditioned CG against fused Jacobi-PCG and unpreconditioned
+fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
+
+  python scripts/pmg_compare.py --degree 3 --perturb 0.2 --kappa random [--ndofs 20000000]
+  python scripts/pmg_compare.py --degree 6 --perturb 0.0 --kappa constant
+
+One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
+its own auto-selected operator:
+
+  cg_fused   DeviceCG(pb)                          fused CG, native runtime
+  pcg_fused  DeviceCG(pb, "jacobi", loop="fused")  fused Jacobi-PCG, native runtime
+  pmg        DeviceCG(pb, "pmg")                   generic loop + one V-cycle per iteration
+
+Per-iteration time: device events between the steps of `iterate_timed(n)`, per
+window the mean of the first n - 1 steps, per variant the median over the
+windows (min, max), the variants interleaved window by window after two
+warm-up windows each.  Iterations to the tolerance use the recurrence residual
+(`residual_norm2()` read back after every iteration, outside the timed
+windows).  The time to the tolerance of pmg is also measured directly: the
+wall time of start + iterate(k) + a device synchronisation, median of three.
+The V-cycle's parts are timed alone with device events (median of `--reps`
+batches of five calls).  Bandwidths count the owned entries a kernel must move
+(cheb_step: 5 reads + 2 writes; prolong: coarse read + fine write; restrict:
+fine read + coarse read and write); the stream rate is a 2-read 1-write torch
+update of vectors of the problem's size.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--degree", type=int, default=3)
+    ap.add_argument("--ndofs", type=int, default=20_000_000)
+    ap.add_argument("--perturb", type=float, default=0.2)
+    ap.add_argument("--kappa", default="random", choices=["constant", "random"])
+    ap.add_argument("--iters", type=int, default=10, help="iterations per timed window")
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--tol", type=float, default=1e-8)
+    ap.add_argument("--max-iter", type=int, default=6000)
+    a = ap.parse_args(argv)
+
+    import torch
+
+    from benchmark_dolfinx_amd.driver import make_operator
+    from benchmark_dolfinx_amd.fem.mesh import compute_mesh_size
+    from benchmark_dolfinx_amd.models.poisson import PoissonProblem
+    from benchmark_dolfinx_amd.parallel.comm import Comm
+    from benchmark_dolfinx_amd.solvers.cg import DeviceCG
+
+    if not torch.cuda.is_available():
+        raise SystemExit("pmg_compare needs a GPU (no timing is taken without one)")
+    torch.cuda.set_device(0)
+    nx = compute_mesh_size(a.ndofs, a.degree)
+    pb = PoissonProblem(Comm(), nx, a.degree, 1, False, torch.float64, "gpu", a.perturb, a.kappa)
+    b = pb.assemble_rhs()
+
+    def make(variant):
+        op = make_operator(pb)
+        if variant == "cg_fused":
+            cg = DeviceCG(pb)
+        elif variant == "pcg_fused":
+            cg = DeviceCG(pb, "jacobi", loop="fused")
+        else:
+            cg = DeviceCG(pb, "pmg")
+        x = pb.new_vector()
+        cg.start(op, x, b)
+        return op, cg, x
+
+    variants = ("cg_fused", "pcg_fused", "pmg")
+    state = {v: make(v) for v in variants}
+    pmg = state["pmg"][1].pmg
+
+    def window(v):
+        steps = state[v][1].iterate_timed(a.iters)
+        torch.cuda.synchronize()
+        return sum(steps[:-1]) / (len(steps) - 1)
+
+    for _ in range(2):
+        for v in variants:
+            window(v)
+    samples = {v: [] for v in variants}
+    for _ in range(a.windows):
+        for v in variants:
+            samples[v].append(window(v))
+    ms = {v: {"median": statistics.median(s), "min": min(s), "max": max(s)}
+          for v, s in samples.items()}
+
+    iters = {}
+    for v in variants:
+        op, cg, x = state[v]
+        cg.start(op, x.zero_(), b)
+        rr0 = cg.residual_norm2()
+        k = 0
+        while k < a.max_iter:
+            cg.iterate(1)
+            k += 1
+            if cg.residual_norm2() < a.tol * a.tol * rr0:
+                break
+        iters[v] = k if k < a.max_iter else None
+
+    # pmg: the whole solve, wall clock
+    wall = []
+    if iters["pmg"]:
+        op, cg, x = state["pmg"]
+        for _ in range(3):
+            x.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cg.start(op, x, b)
+            cg.iterate(iters["pmg"])
+            torch.cuda.synchronize()
+            wall.append(time.perf_counter() - t0)
+        y = pb.new_vector()
+        op.apply(x.clone(), y)
+        true_res = pb.norm(b - y) / pb.norm(b)
+    else:
+        true_res = None
+
+    # the V-cycle's parts, each alone
+    def timed(fn):
+        out = []
+        fn()
+        torch.cuda.synchronize()
+        for _ in range(a.reps):
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            for _ in range(5):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            out.append(e0.elapsed_time(e1) / 5)
+        return statistics.median(out)
+
+    lv = pmg.levels[0]
+    r, z = state["pmg"][1].r, state["pmg"][1].z
+    coef = lv.coef[-1]
+    parts = {"cycle": timed(lambda: pmg.apply(r, z)),
+             "fine_apply": timed(lambda: lv.op.apply(z, lv.y)),
+             "cheb_step": timed(lambda: lv.k.cheb_step(False, coef[0], coef[1], lv.dinv, r, lv.y,
+                                                       lv.d, z)),
+             "cheb_step_first": timed(lambda: lv.k.cheb_step(True, 0.0, coef[1], lv.dinv, r, None,
+                                                             lv.d, z)),
+             "axpy": timed(lambda: lv.k.axpy(lv.t, -1.0, lv.y, r))}
+    bw = {}
+    if len(pmg.levels) > 1:
+        nxt = pmg.levels[1]
+        parts["restrict"] = timed(lambda: pmg.restrict(0, lv.t, nxt.r))
+        parts["prolong"] = timed(lambda: pmg.prolong(0, nxt.z, lv.t))
+        parts["restrict_kernel"] = timed(lambda: lv.k.restrict(nxt.latd, lv.J, lv.t, nxt.r))
+        parts["coarse_levels"] = timed(lambda: pmg._vcycle(1, nxt.r, nxt.z))
+        nc_ = nxt.pb.lat.ndofs_local
+        nf_ = pb.lat.ndofs_local
+        bw["prolong_tb_s"] = 8 * (nc_ + nf_) / (parts["prolong"] * 1e-3) / 1e12
+        bw["restrict_kernel_tb_s"] = 8 * (nf_ + 2 * nc_) / (parts["restrict_kernel"] * 1e-3) / 1e12
+    nown = pb.lat.ndofs_owned
+    bw["cheb_step_tb_s"] = 8 * 7 * nown / (parts["cheb_step"] * 1e-3) / 1e12
+    bw["cheb_step_first_tb_s"] = 8 * 4 * nown / (parts["cheb_step_first"] * 1e-3) / 1e12
+    napply = 2 * len(lv.coef)  # pre: k - 1, residual: 1, post: k
+    parts["fine_applies_per_cycle"] = napply if len(pmg.levels) > 1 else len(lv.coef) - 1
+
+    n = pb.new_vector().numel()
+    sr, sy = (torch.rand(n, dtype=torch.float64, device="cuda") for _ in range(2))
+    stream_ms = timed(lambda: sr.add_(sy, alpha=-1e-9))
+    stream_tbs = 3 * 8 * n / (stream_ms * 1e-3) / 1e12
+
+    rec = {"degree": a.degree, "perturb": a.perturb, "kappa": a.kappa, "mesh": list(nx),
+           "ndofs": pb.ndofs_global, "kernel": state["cg_fused"][0].name,
+           "level_kernels": [getattr(v.op, "name", type(v.op).__name__) for v in pmg.levels],
+           "pmg": pmg.info(), "ms_per_iter": ms, "tol": a.tol, "iters_to_tol": iters,
+           "time_to_tol_s": {v: (iters[v] * ms[v]["median"] * 1e-3 if iters.get(v) else None)
+                             for v in iters},
+           "pmg_wall_s": {"median": statistics.median(wall), "min": min(wall), "max": max(wall)}
+           if wall else None,
+           "pmg_true_residual": true_res, "cycle_parts_ms": parts, "bandwidth": bw,
+           "stream_2r1w": {"ms": stream_ms, "tb_per_s": stream_tbs},
+           "device": torch.cuda.get_device_name(0)}
+    pmg.close()
+    for op, _, _ in state.values():
+        op.close()
+    print(json.dumps(rec), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
