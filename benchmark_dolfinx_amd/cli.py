@@ -14,7 +14,8 @@ fused,v1,dofmap}, --geometry {auto,otf,otf-general,stored}, --kappa {constant,ra
 --warmup N (untimed repetitions before the timed loop), --precond {none,jacobi,pmg}
 (with --cg: CG preconditioned with the matrix-free operator diagonal, or with
 a p-multigrid V-cycle; --pmg_smooth N / --pmg_coarse N: Chebyshev degree of
-its smoothers / of its degree-1 coarse solve),
+its smoothers / of its coarsest-level solve; --pmg_hlevels N: geometric
+h-levels under its degree-1 level, -1 = as many as the mesh allows),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -80,7 +81,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pmg_smooth", type=int, default=2,
                     help="Chebyshev degree of the p-multigrid smoothers (--precond pmg)")
     ap.add_argument("--pmg_coarse", type=int, default=8,
-                    help="Chebyshev degree of the p-multigrid degree-1 solve (--precond pmg)")
+                    help="Chebyshev degree of the p-multigrid coarsest-level solve (degree 1, or "
+                         "the last h-level; --precond pmg)")
+    ap.add_argument("--pmg_hlevels", type=int, default=0,
+                    help="Geometric h-levels under the p-multigrid's degree-1 level (--cg "
+                         "--precond pmg): 0 = none, N = at most N, -1 = as many as the mesh allows")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -101,6 +106,10 @@ def parse_args(argv=None):
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
         raise SystemExit("error: Options 'pmg_smooth' and 'pmg_coarse' must be positive")
+    if args.pmg_hlevels < -1:
+        raise SystemExit("error: Option 'pmg_hlevels' must be -1, 0 or a positive count")
+    if args.pmg_hlevels != 0 and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_hlevels' needs 'cg' and 'precond pmg'")
     if args.pcg_loop == "fused" and not args.cg:
         raise SystemExit("error: Option 'pcg_loop fused' needs 'cg'")
     if args.pcg_loop == "fused" and args.precond != "jacobi":
@@ -200,7 +209,8 @@ def run_benchmark(comm, nx, args, platform):
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,
                          pmg_opts={"smooth_degree": args.pmg_smooth,
-                                   "coarse_degree": args.pmg_coarse})
+                                   "coarse_degree": args.pmg_coarse,
+                                   "h_levels": args.pmg_hlevels})
     t = res.mat_free_time
     gdofs = pb.ndofs_global * args.nreps / (1e9 * t) if t > 0 else 0.0
     out = {"ncells_global": pb.ncells_global, "ndofs_global": pb.ndofs_global,

@@ -946,6 +946,107 @@ int restrict_host(const int64_t* latc, const int64_t* latf, const double* Jd, co
   return 0;
 }
 
+// ------------------------------------------------- h-multigrid transfers
+// Host twins of csrc/hip/lap_htransfer.h: trilinear interpolation in index
+// space between two degree-1 lattices and its transpose; cidx / cw (fine
+// lengths) and fpos (coarse lengths) hold the three axes one after the other.
+inline bool htransfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
+  if (lc.tsy || lf.tsy) return false;
+  if (lc.P != 1 || lf.P != 1) return false;
+  for (int a = 0; a < 3; ++a) {
+    if (lc.gh[a] != lf.gh[a]) return false;
+    if (lc.n[a] < 0 || lc.n[a] > lf.n[a]) return false;
+    if (lc.L[a] != lc.n[a] + 1 || lf.L[a] != lf.n[a] + 1) return false;
+    if (lf.L[a] > 0x7fffffffLL) return false;
+  }
+  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
+}
+
+// vf (+)= P vc: a + w (b - a) per axis, z then y then x; an axis with w = 0
+// takes a and reads nothing else.  add: owned fine nodes only.
+template <typename T>
+int hprolong_host(const int64_t* latc, const int64_t* latf, const int* cidx, const T* cw,
+                  const int* fpos, const T* vc, T* vf, int add) {
+  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
+  if (!htransfer_pair_ok(lc, lf) || !cidx || !cw || !fpos || !vc || !vf) return 1;
+  const int* cx[3] = {cidx, cidx + lf.L[0], cidx + lf.L[0] + lf.L[1]};
+  const T* w[3] = {cw, cw + lf.L[0], cw + lf.L[0] + lf.L[1]};
+  const int64_t e[3] = {add ? lf.L[0] - lf.gh[0] : lf.L[0], add ? lf.L[1] - lf.gh[1] : lf.L[1],
+                        add ? lf.L[2] - lf.gh[2] : lf.L[2]};
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t i = 0; i < e[0]; ++i)
+    for (int64_t j = 0; j < e[1]; ++j) {
+      const int64_t ci = cx[0][i], cj = cx[1][j];
+      const T wi = w[0][i], wj = w[1][j];
+      const int na = wi != 0 ? 2 : 1, nb = wj != 0 ? 2 : 1;
+      for (int64_t k = 0; k < e[2]; ++k) {
+        const int64_t ck = cx[2][k];
+        const T wk = w[2][k];
+        T gx[2] = {0, 0};
+        for (int a = 0; a < na; ++a) {
+          T gy[2] = {0, 0};
+          for (int b = 0; b < nb; ++b) {
+            const int64_t at = lc.idx(ci + a, cj + b, ck);
+            T v = vc[at];
+            if (wk != 0) v += wk * (vc[at + 1] - v);
+            gy[b] = v;
+          }
+          gx[a] = nb == 2 ? gy[0] + wj * (gy[1] - gy[0]) : gy[0];
+        }
+        const T out = na == 2 ? gx[0] + wi * (gx[1] - gx[0]) : gx[0];
+        const int64_t to = lf.idx(i, j, k);
+        vf[to] = add ? vf[to] + out : out;
+      }
+    }
+  return 0;
+}
+
+// vc = P^T (vf - y) (y null: P^T vf): every local coarse node gathers the
+// owned fine nodes strictly between its coarse neighbours, ascending, x
+// outermost, with the weights cw, 1, 1 - cw.
+template <typename T>
+int hrestrict_host(const int64_t* latc, const int64_t* latf, const int* cidx, const T* cw,
+                   const int* fpos, const T* vf, const T* y, T* vc) {
+  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
+  if (!htransfer_pair_ok(lc, lf) || !cidx || !cw || !fpos || !vc || !vf) return 1;
+  const T* w[3] = {cw, cw + lf.L[0], cw + lf.L[0] + lf.L[1]};
+  const int* fp[3] = {fpos, fpos + lc.L[0], fpos + lc.L[0] + lc.L[1]};
+  auto range = [&](int a, int64_t j, int64_t& lo, int64_t& mid, int64_t& hi) {
+    mid = fp[a][j];
+    lo = j > 0 ? fp[a][j - 1] + 1 : mid;
+    hi = j < lc.L[a] - 1 ? fp[a][j + 1] - 1 : mid;
+    hi = std::min<int64_t>(hi, lf.L[a] - lf.gh[a] - 1);
+  };
+  auto weight = [&](int a, int64_t f, int64_t mid) {
+    return f < mid ? w[a][f] : (f == mid ? T(1) : T(1) - w[a][f]);
+  };
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t i = 0; i < lc.L[0]; ++i)
+    for (int64_t j = 0; j < lc.L[1]; ++j)
+      for (int64_t k = 0; k < lc.L[2]; ++k) {
+        int64_t lo[3], mid[3], hi[3];
+        range(0, i, lo[0], mid[0], hi[0]);
+        range(1, j, lo[1], mid[1], hi[1]);
+        range(2, k, lo[2], mid[2], hi[2]);
+        T sx = 0;
+        for (int64_t fi = lo[0]; fi <= hi[0]; ++fi) {
+          T sy = 0;
+          for (int64_t fj = lo[1]; fj <= hi[1]; ++fj) {
+            T sz = 0;
+            for (int64_t fk = lo[2]; fk <= hi[2]; ++fk) {
+              const int64_t at = lf.idx(fi, fj, fk);
+              const T v = y ? vf[at] - y[at] : vf[at];
+              sz += weight(2, fk, mid[2]) * v;
+            }
+            sy += weight(1, fj, mid[1]) * sz;
+          }
+          sx += weight(0, fi, mid[0]) * sy;
+        }
+        vc[lc.idx(i, j, k)] = sx;
+      }
+  return 0;
+}
+
 // Host twin of bdx_cheb_step (csrc/hip/blas.hip) over the owned rows.
 template <typename T>
 void cheb_step_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, int first, T a,
@@ -1088,6 +1189,19 @@ int bdx_host_version() { return 1; }
   int bdx_cpu_restrict_##SUF(const int64_t* latc, const int64_t* latf,        \
                              const double* J, const T* vf, T* vc) {           \
     return restrict_host<T>(latc, latf, J, vf, vc);                           \
+  }                                                                           \
+  /* h-multigrid transfers between the degree-1 lattices latc / latf with   */ \
+  /* the tables cidx, cw, fpos: vf (+)= P vc, vc = P^T (vf - y); the host    */ \
+  /* twins of bdx_hprolong / bdx_hrestrict, nonzero for a bad pair          */ \
+  int bdx_cpu_hprolong_##SUF(const int64_t* latc, const int64_t* latf,        \
+                             const int* cidx, const T* cw, const int* fpos,   \
+                             const T* vc, T* vf, int add) {                   \
+    return hprolong_host<T>(latc, latf, cidx, cw, fpos, vc, vf, add);         \
+  }                                                                           \
+  int bdx_cpu_hrestrict_##SUF(const int64_t* latc, const int64_t* latf,       \
+                              const int* cidx, const T* cw, const int* fpos,  \
+                              const T* vf, const T* y, T* vc) {               \
+    return hrestrict_host<T>(latc, latf, cidx, cw, fpos, vf, y, vc);          \
   }                                                                           \
   /* Chebyshev step d = a d + b dinv (r - y); z += d (first: d = z = b dinv */ \
   /* r), the host twin of bdx_cheb_step                                    */ \

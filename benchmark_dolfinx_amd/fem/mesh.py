@@ -296,6 +296,103 @@ def make_local_lattice(rank: int, nranks: int, ncells: tuple[int, int, int],
     return LocalLattice(rank, nranks, degree, tuple(ncells), pgrid, rc, c0, c1)
 
 
+def axis_cuts(lat: LocalLattice) -> list[list[int]]:
+    """Per axis the global cell index of every rank cut, [0, ..., ncells]:
+    the floor(n r / p) cuts of `make_local_lattice`, or the cuts a coarsened
+    lattice carries (`coarsened_lattice`)."""
+    cuts = getattr(lat, "cuts", None)
+    if cuts is not None:
+        return [list(c) for c in cuts]
+    return [[(lat.ncells_global[d] * r) // lat.pgrid[d] for r in range(lat.pgrid[d] + 1)]
+            for d in range(3)]
+
+
+def coarsen_segments(cuts) -> tuple[list[np.ndarray], list[int]]:
+    """Geometric coarsening of one axis whose fine cells [cuts[r], cuts[r + 1])
+    belong to rank segment r (one rank: cuts = [0, n]).
+
+    A segment of n >= 2 fine cells becomes n // 2 coarse cells, the pairs
+    (0, 2), (2, 4), ...; when n is odd the last coarse cell is a triple, so
+    the last cell is at most twice its neighbours at any depth (a lone
+    leftover fine cell would end up 1 / 2^k of them).  A segment of one cell
+    stays one cell.  Every cut is a coarse vertex, so each coarse cell belongs
+    to exactly one rank.
+
+    Returns (fpos, coarse_cuts): fpos[r][j] is the fine vertex index, local
+    to segment r, of its coarse vertex j (fpos[r][0] = 0, fpos[r][-1] = the
+    segment's cells, strictly increasing with steps in {1, 2, 3}), and
+    coarse_cuts the prefix sums of the coarse cells per segment.  When the
+    axis would fall below 2 global coarse cells it is left alone: identity
+    maps and coarse_cuts = cuts.
+    """
+    cuts = [int(c) for c in cuts]
+    fpos, ccuts = [], [0]
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        n = b - a
+        if n < 1:
+            raise ValueError("every rank segment needs at least one cell")
+        f = np.arange(0, n + 1, dtype=np.int64) if n == 1 else \
+            np.append(2 * np.arange(n // 2, dtype=np.int64), n)
+        fpos.append(f)
+        ccuts.append(ccuts[-1] + f.size - 1)
+    if ccuts[-1] < 2:
+        return ([np.arange(0, b - a + 1, dtype=np.int64) for a, b in zip(cuts[:-1], cuts[1:])],
+                list(cuts))
+    return fpos, ccuts
+
+
+def coarsened_lattice(lat: LocalLattice) -> tuple[LocalLattice, list[np.ndarray]]:
+    """The degree-1 lattice one h-level below `lat` (`coarsen_segments` on
+    every axis) and fpos[3], the local fine vertex index of every local coarse
+    vertex per axis.  Pure arithmetic on `ncells_global`, `pgrid` and the cut
+    list, so every rank computes the same global level without communication;
+    partition grid, neighbours and the 1-dof-thick halo pattern are those of
+    `lat`.  An axis that cannot be coarsened keeps the identity map.
+
+    The hierarchy is a function of the partition's cut points: where every cut
+    is an even global vertex index at every level it equals the one-rank
+    hierarchy (and results are partition-invariant to rounding); otherwise a
+    pair straddling a cut is split differently and only the converged
+    solutions agree, to the solver tolerance.
+    """
+    fpos, ccuts, c0, c1 = [], [], [], []
+    for d, cuts in enumerate(axis_cuts(lat)):
+        f, cc = coarsen_segments(cuts)
+        r = lat.rcoord[d]
+        fpos.append(f[r])
+        ccuts.append(cc)
+        c0.append(cc[r])
+        c1.append(cc[r + 1])
+    out = LocalLattice(lat.rank, lat.nranks, 1, tuple(c[-1] for c in ccuts), lat.pgrid,
+                       lat.rcoord, tuple(c0), tuple(c1))
+    out.cuts = ccuts
+    return out, fpos
+
+
+def h_hierarchy(lat: LocalLattice, h_levels: int = -1) -> list[tuple[LocalLattice, list[np.ndarray]]]:
+    """The h-levels below the degree-1 lattice on `lat`'s cells, finest first:
+    (lattice, fpos to it from the level above).  At most `h_levels` (-1: as
+    many as the rule allows).  Full coarsening only: the hierarchy ends when
+    an axis of more than one global cell can no longer be coarsened (a level
+    that coarsens only some of those axes would stretch the cells, which the
+    point-Jacobi smoothers do not handle), or when the next level would have
+    no interior dof.  An axis of one global cell never changes."""
+    if h_levels < -1:
+        raise ValueError("h_levels must be -1 (all), 0 (none) or a positive count")
+    out = []
+    cur = lat
+    while h_levels < 0 or len(out) < h_levels:
+        nxt, fpos = coarsened_lattice(cur)
+        fine_n = cur.ncells_global
+        if any(c == f and f > 1 for c, f in zip(nxt.ncells_global, fine_n)):
+            break
+        if nxt.ncells_global == tuple(fine_n) or any(c < 2 for c in nxt.ncells_global):
+            break
+        out.append((nxt, fpos))
+        cur = nxt
+    return out
+
+
 def vertex_coordinates(lat: LocalLattice, perturb: float = 0.0,
                        seed: int = 42, shear: float = 0.0) -> np.ndarray:
     """Local vertex lattice coordinates, shape (nx+1, ny+1, nz+1, 3).

@@ -89,7 +89,11 @@ class PoissonProblem:
     def __init__(self, comm: Comm, ncells, degree: int, qmode: int = 1,
                  use_gauss: bool = False, dtype=torch.float64, platform: str = "gpu",
                  perturb: float = 0.0, coefficient: str = "constant", shear: float = 0.0,
-                 partition: str | None = None):
+                 partition: str | None = None, lat: LocalLattice | None = None,
+                 xv: np.ndarray | None = None, kc: np.ndarray | None = None):
+        """`lat`, `xv`, `kc` (default None: the box mesh of `ncells`): build the
+        problem on a given lattice with given local vertices (n + 1 per axis,
+        x 3) and per-cell kappa (None: the constant) instead; see `coarsened`."""
         if use_gauss and qmode == 0:
             # same validation as the reference (src/laplacian.hpp:197-198, Q5)
             raise RuntimeError("Expecting identity matrix for qmode=0")
@@ -111,11 +115,20 @@ class PoissonProblem:
         if partition not in ("yz", "xyz"):
             raise ValueError(f"unknown partition policy {partition!r}")
         self.partition = partition
-        self.lat: LocalLattice = make_local_lattice(comm.rank, comm.size, tuple(ncells), degree,
-                                                    whole_x=partition == "yz")
+        given = lat is not None
+        if given and (xv is None or lat.degree != degree or tuple(lat.ncells_global) != tuple(ncells)
+                      or tuple(xv.shape) != tuple(m + 1 for m in lat.n) + (3,)
+                      or (kc is not None and tuple(kc.shape) != tuple(lat.n))):
+            raise ValueError("a given lattice needs its degree, cell counts, vertices and kappa")
+        if not given and (xv is not None or kc is not None):
+            raise ValueError("xv and kc are given together with lat")
+        self.lat: LocalLattice = lat if given else make_local_lattice(
+            comm.rank, comm.size, tuple(ncells), degree, whole_x=partition == "yz")
         npdt = _np_dtype(dtype)
         with timed("~setup mesh"):
-            xv = vertex_coordinates(self.lat, perturb, shear=shear).astype(npdt)
+            if not given:
+                xv = vertex_coordinates(self.lat, perturb, shear=shear)
+            xv = xv.astype(npdt)
             self.xv_host = np.ascontiguousarray(xv)
             self.xv = torch.from_numpy(self.xv_host).to(self.device)
         self.host_tables = {k: np.ascontiguousarray(v, dtype=npdt) for k, v in dict(
@@ -134,11 +147,39 @@ class PoissonProblem:
         self.all_x_trilinear = cells_x_trilinear(self.xv_host)
         # per-cell kappa (None: the reference's constant kappa = 2)
         self.coefficient = coefficient
-        kc = cell_coefficients(self.lat, coefficient, KAPPA)
+        if not given:
+            kc = cell_coefficients(self.lat, coefficient, KAPPA)
         self.kc_host = None if kc is None else np.ascontiguousarray(kc, dtype=npdt)
         self.kc = None if kc is None else torch.from_numpy(self.kc_host).to(self.device)
         self._diag = None  # operator_diagonal() / jacobi_inverse() caches
         self._dinv = None
+
+    @classmethod
+    def coarsened(cls, parent: "PoissonProblem", lat: LocalLattice, fpos) -> "PoissonProblem":
+        """The degree-1 problem on the h-coarsened lattice `lat` of `parent`'s
+        cells (`fem.mesh.coarsened_lattice`; fpos[a]: the parent's local vertex
+        index of every coarse vertex).  The vertices are the parent's at fpos
+        (its perturbation carries over), kappa the arithmetic mean over each
+        coarse cell's children (None when the parent's is), the geometry flags
+        are recomputed; quadrature, dtype, platform and comm are the parent's.
+        The operator on it is rediscretised, not a Galerkin product."""
+        fpos = [np.asarray(f, dtype=np.int64) for f in fpos]
+        for a in range(3):
+            if fpos[a].size != lat.n[a] + 1 or fpos[a][0] != 0 or fpos[a][-1] != parent.lat.n[a] \
+                    or np.any(np.diff(fpos[a]) < 1):
+                raise ValueError("fpos does not map the coarse lattice onto the parent's vertices")
+        xv = parent.xv_host[np.ix_(fpos[0], fpos[1], fpos[2])]
+        kc = None
+        if parent.kc_host is not None:
+            kc = parent.kc_host.astype(np.float64)
+            for a in range(3):
+                kc = np.add.reduceat(kc, fpos[a][:-1], axis=a)
+                shape = [1, 1, 1]
+                shape[a] = lat.n[a]
+                kc = kc / np.diff(fpos[a]).reshape(shape)
+        return cls(parent.comm, lat.ncells_global, 1, parent.qmode, parent.use_gauss, parent.dtype,
+                   parent.platform, parent.perturb, parent.coefficient, shear=parent.shear,
+                   partition=parent.partition, lat=lat, xv=xv, kc=kc)
 
     # --------------------------------------------------------------- vectors
     @property

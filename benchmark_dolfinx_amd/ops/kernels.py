@@ -46,6 +46,42 @@ class TableSet:
         self.qpts = np.ascontiguousarray(tables.qpts, dtype=np.float64)
 
 
+class HTransferTables:
+    """Tables of one h-multigrid level pair (csrc/hip/lap_htransfer.h), on
+    `device`: from `fpos[a]`, the fine vertex index of every coarse vertex of
+    axis a (strictly increasing from 0 to the last fine vertex),
+    cidx[a][i] = the lower coarse neighbour of fine node i, cw[a][i] = the
+    weight (i - lo) / (hi - lo) of its upper neighbour, exactly 0 (and cidx =
+    the node itself) where i is a coarse node.  The three axes are stored one
+    after the other."""
+
+    def __init__(self, fpos, dtype, device):
+        cidx, cw, fp = [], [], []
+        for f in fpos:
+            f = np.asarray(f, dtype=np.int64)
+            if f.ndim != 1 or f.size < 1 or f[0] != 0 or np.any(np.diff(f) < 1):
+                raise ValueError("fpos must increase strictly from 0")
+            i = np.arange(int(f[-1]) + 1)
+            lo = np.searchsorted(f, i, side="right") - 1       # f[lo] <= i
+            hi = np.minimum(lo + 1, f.size - 1)
+            span = np.maximum(f[hi] - f[lo], 1)
+            cidx.append(lo)
+            cw.append((i - f[lo]) / span)                       # 0 at coarse nodes
+            fp.append(f)
+        self.Lf = tuple(int(f[-1]) + 1 for f in fp)
+        self.Lc = tuple(int(f.size) for f in fp)
+        self.fpos_host = fp
+        self.cidx = torch.from_numpy(np.concatenate(cidx).astype(np.int32)).to(device)
+        self.cw = torch.from_numpy(np.concatenate(cw)).to(device, dtype)
+        self.fpos = torch.from_numpy(np.concatenate(fp).astype(np.int32)).to(device)
+
+    def check(self, latd_c, latd_f) -> None:
+        """The tables' extents are those of the two lattice descriptors (the
+        kernels index the tables by lattice node)."""
+        if tuple(latd_c[3:6]) != self.Lc or tuple(latd_f[3:6]) != self.Lf:
+            raise ValueError("h-transfer tables do not belong to this lattice pair")
+
+
 class HipKernels:
     """Bound kernel launchers for one problem (lattice + tables + dtype)."""
 
@@ -206,6 +242,22 @@ class HipKernels:
         _check(self._f("bdx_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc),
                                        _stream()), "restrict")
 
+    def hprolong(self, latd_c, tab: HTransferTables, vc, vf, add: bool = False):
+        """h-multigrid: vf = P vc on every node of this (fine, degree-1)
+        lattice, or with `add` vf += P vc on its owned nodes (lap_htransfer.h)."""
+        tab.check(latd_c, self.latd)
+        _check(self._f("bdx_hprolong")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
+                                       ptr(tab.fpos), ptr(vc), ptr(vf), int(add), _stream()),
+               "hprolong")
+
+    def hrestrict(self, latd_c, tab: HTransferTables, vf, y, vc):
+        """h-multigrid: vc = P^T (vf - y) over the owned fine nodes (y None:
+        P^T vf), every local coarse node written; one launch, no atomics."""
+        tab.check(latd_c, self.latd)
+        _check(self._f("bdx_hrestrict")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
+                                        ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc), _stream()),
+               "hrestrict")
+
     def box_copy(self, mode: int, vec, lat, side, buf):
         _check(self._f("bdx_box_copy")(mode, ptr(vec), lat.L[1], lat.ld, ptr(side.table),
                                        len(side.boxes), side.total, ptr(buf), _stream()),
@@ -243,6 +295,18 @@ class HostKernels:
     def restrict(self, latd_c, J, vf, vc):
         if self._f("bdx_cpu_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc)):
             raise ValueError("restrict: lattice pair outside the p-multigrid schedule")
+
+    def hprolong(self, latd_c, tab: HTransferTables, vc, vf, add: bool = False):
+        tab.check(latd_c, self.latd)
+        if self._f("bdx_cpu_hprolong")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
+                                       ptr(tab.fpos), ptr(vc), ptr(vf), int(add)):
+            raise ValueError("hprolong: not a pair of degree-1 lattices of one partition")
+
+    def hrestrict(self, latd_c, tab: HTransferTables, vf, y, vc):
+        tab.check(latd_c, self.latd)
+        if self._f("bdx_cpu_hrestrict")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
+                                        ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc)):
+            raise ValueError("hrestrict: not a pair of degree-1 lattices of one partition")
 
     def axpy(self, out, alpha: float, x, y):
         o = self.o

@@ -82,6 +82,8 @@ def host():
                 _declare(lib, f"bdx_cpu_interp_f_{suf}", [vp, vp, vp, vp])
                 _declare(lib, f"bdx_cpu_prolong_{suf}", [vp, vp, vp, vp, vp], i32)
                 _declare(lib, f"bdx_cpu_restrict_{suf}", [vp, vp, vp, vp, vp], i32)
+                _declare(lib, f"bdx_cpu_hprolong_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32], i32)
+                _declare(lib, f"bdx_cpu_hrestrict_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp], i32)
                 _declare(lib, f"bdx_cpu_cheb_step_{suf}",
                          [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
             _host = lib

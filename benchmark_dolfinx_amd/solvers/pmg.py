@@ -23,6 +23,17 @@ llo) / 2, delta = (lhi - llo) / 2, sigma = theta / delta, rho_0 = 1 / sigma
 All coefficients are host doubles fixed at setup, so a cycle runs without any
 host synchronisation: operator applies, one fused vector kernel per Chebyshev
 step (`cheb_step`), axpy, the two transfer kernels and the halo exchanges.
+
+h-levels (`h_levels != 0`, off by default): the hierarchy continues below
+degree 1 with geometrically coarsened degree-1 problems on the lattices of
+`fem.mesh.h_hierarchy` (`PoissonProblem.coarsened`: subsampled vertices, the
+children's mean kappa, rediscretised operator and diagonal).  The levels form
+one list, the p-levels then the h-levels; every level but the last is smoothed
+and the last takes the coarse iteration, so degree 1 becomes an ordinary
+smoothed level.  Between two degree-1 levels the transfers are trilinear in
+index space (csrc/hip/lap_htransfer.h) and fold the cycle's two vector passes:
+r_c = R (r - A z) in the restriction's load, z += P z_c in the prolongation's
+store.  The exchange protocol around them is that of the p-transfers.
 """
 
 from __future__ import annotations
@@ -30,7 +41,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from ..fem.mesh import _hash_uniform
+from ..fem.mesh import _hash_uniform, h_hierarchy
 from ..fem.quadrature import lagrange_tables
 from ..models.poisson import PoissonProblem
 
@@ -75,7 +86,8 @@ class _Level:
         self.t = pb.new_vector()    # residual, then the prolonged correction
         self.r = None               # coarse levels: the restricted residual
         self.z = None               # coarse levels: the correction
-        self.J = None               # table to the next coarser level
+        self.J = None               # p-transfer table to the next coarser level
+        self.H = None               # or the h-transfer tables to it
         self.coef = []
         self.lambda_max = 0.0
 
@@ -84,14 +96,22 @@ class PMultigrid:
     """z = M^-1 r by one p-multigrid V-cycle (module docstring).
 
     degrees: the level degrees; lambda_max: the estimate of lambda_max(D^-1 A)
-    per level (the smoothers' upper bound is 1.1 x it)."""
+    per level (the smoothers' upper bound is 1.1 x it).
+
+    h_levels: 0 = the p-levels only; N > 0 = at most N geometric h-levels
+    under degree 1; -1 = as many as `fem.mesh.h_hierarchy` allows.  `h_levels`
+    then holds the number built and `h_cells` their global cell counts; the
+    hierarchy depends on the partition's cut points (fem/mesh.py)."""
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
-                 coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10):
+                 coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
+                 h_levels: int = 0):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
             raise ValueError("smoother ranges must exceed 1")
+        if isinstance(h_levels, bool) or not isinstance(h_levels, (int, np.integer)) or h_levels < -1:
+            raise ValueError("h_levels must be -1 (all), 0 (none) or a positive count")
         self.pb = pb
         self.smooth_degree, self.smooth_range = int(smooth_degree), float(smooth_range)
         self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
@@ -106,9 +126,23 @@ class PMultigrid:
             if i > 0:
                 lv.r, lv.z = lpb.new_vector(), lpb.new_vector()
             self.levels.append(lv)
+        # h-levels under degree 1 (fem/mesh.py: h_hierarchy), each a degree-1
+        # problem on the coarsened lattice; lv.H: the tables to the next one
+        self.h_cells: list[tuple[int, int, int]] = []
+        if h_levels != 0:
+            from ..ops.kernels import HTransferTables
+            for lat, fpos in h_hierarchy(self.levels[-1].pb.lat, int(h_levels)):
+                above = self.levels[-1]
+                lv = _Level(PoissonProblem.coarsened(above.pb, lat, fpos))
+                lv.r, lv.z = lv.pb.new_vector(), lv.pb.new_vector()
+                above.H = HTransferTables(fpos, pb.dtype, pb.device)
+                self.levels.append(lv)
+                self.h_cells.append(tuple(int(c) for c in lat.ncells_global))
+        self.h_levels_requested = int(h_levels)
+        self.h_levels = len(self.h_cells)                   # the number built
         for i, lv in enumerate(self.levels):
             coarsest = i == len(self.levels) - 1
-            if not coarsest:
+            if not coarsest and lv.H is None:
                 nxt = self.levels[i + 1].pb
                 J, _ = lagrange_tables(nxt.tables.nodes, lv.pb.tables.nodes)
                 lv.J = np.ascontiguousarray(J, dtype=np.float64)
@@ -146,20 +180,33 @@ class PMultigrid:
         return float(lam)
 
     # ------------------------------------------------------------ transfers
-    def prolong(self, l: int, vc: torch.Tensor, vf: torch.Tensor) -> None:
+    def prolong(self, l: int, vc: torch.Tensor, vf: torch.Tensor, add: bool = False) -> None:
         """vf = P vc from level l + 1 to level l (every local fine node; the
-        coarse ghost planes are read, so vc is forward-exchanged first)."""
+        coarse ghost planes are read, so vc is forward-exchanged first).
+        `add` (h-pairs only): vf += P vc on the owned fine nodes instead."""
         fine, coarse = self.levels[l], self.levels[l + 1]
         coarse.pb.halo.forward(vc)
+        if fine.H is not None:
+            fine.k.hprolong(coarse.latd, fine.H, vc, vf, add)
+            return
+        if add:
+            raise ValueError("prolong(add=True) is the h-transfer's mode")
         fine.k.prolong(coarse.latd, fine.J, vc, vf)
 
-    def restrict(self, l: int, vf: torch.Tensor, vc: torch.Tensor) -> None:
+    def restrict(self, l: int, vf: torch.Tensor, vc: torch.Tensor,
+                 y: torch.Tensor | None = None) -> None:
         """vc = P^T vf from level l to level l + 1: owned fine dofs only, the
         partial sums on the coarse ghost planes reverse-exchanged to their
-        owners, Dirichlet entries zeroed, then forwarded to the ghosts."""
+        owners, Dirichlet entries zeroed, then forwarded to the ghosts.
+        `y` (h-pairs only): vc = P^T (vf - y)."""
         fine, coarse = self.levels[l], self.levels[l + 1]
-        vc.zero_()
-        fine.k.restrict(coarse.latd, fine.J, vf, vc)
+        if fine.H is not None:
+            fine.k.hrestrict(coarse.latd, fine.H, vf, y, vc)
+        else:
+            if y is not None:
+                raise ValueError("restrict(y=) is the h-transfer's mode")
+            vc.zero_()
+            fine.k.restrict(coarse.latd, fine.J, vf, vc)
         coarse.pb.halo.reverse(vc)
         vc.masked_fill_(coarse.bc, 0.0)
         coarse.pb.halo.forward(vc)
@@ -181,11 +228,18 @@ class PMultigrid:
             return
         nxt = self.levels[l + 1]
         lv.op.apply(z, lv.y)
-        lv.k.axpy(lv.t, -1.0, lv.y, r)          # res = r - A z
-        self.restrict(l, lv.t, nxt.r)
-        self._vcycle(l + 1, nxt.r, nxt.z)
-        self.prolong(l, nxt.z, lv.t)
-        lv.k.axpy(z, 1.0, lv.t, z)              # z += P z_c
+        if lv.H is not None:
+            # h-pair: the residual and the correction's sum are folded into
+            # the transfer kernels' load and store
+            self.restrict(l, r, nxt.r, lv.y)    # r_c = R (r - A z)
+            self._vcycle(l + 1, nxt.r, nxt.z)
+            self.prolong(l, nxt.z, z, True)     # z += P z_c
+        else:
+            lv.k.axpy(lv.t, -1.0, lv.y, r)          # res = r - A z
+            self.restrict(l, lv.t, nxt.r)
+            self._vcycle(l + 1, nxt.r, nxt.z)
+            self.prolong(l, nxt.z, lv.t)
+            lv.k.axpy(z, 1.0, lv.t, z)              # z += P z_c
         self._smooth(lv, r, z, False)
 
     def apply(self, r: torch.Tensor, z: torch.Tensor) -> None:
@@ -194,8 +248,12 @@ class PMultigrid:
         self._vcycle(0, r, z)
 
     def info(self) -> dict:
-        return {"degrees": list(self.degrees), "lambda_max": list(self.lambda_max),
-                "smooth_degree": self.smooth_degree, "coarse_degree": self.coarse_degree}
+        out = {"degrees": list(self.degrees), "lambda_max": list(self.lambda_max),
+               "smooth_degree": self.smooth_degree, "coarse_degree": self.coarse_degree}
+        if self.h_levels_requested != 0:
+            out["h_levels"] = self.h_levels
+            out["h_cells"] = [list(c) for c in self.h_cells]
+        return out
 
     def close(self) -> None:
         """Close the level operators (native runtimes, if any was started)."""

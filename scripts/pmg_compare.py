@@ -4,6 +4,7 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
 
   python scripts/pmg_compare.py --degree 3 --perturb 0.2 --kappa random [--ndofs 20000000]
   python scripts/pmg_compare.py --degree 6 --perturb 0.0 --kappa constant
+  python scripts/pmg_compare.py --degree 3 --hlevels -1      (adds the hpmg column, profiles/hpmg.md)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -11,6 +12,9 @@ its own auto-selected operator:
   cg_fused   DeviceCG(pb)                          fused CG, native runtime
   pcg_fused  DeviceCG(pb, "jacobi", loop="fused")  fused Jacobi-PCG, native runtime
   pmg        DeviceCG(pb, "pmg")                   generic loop + one V-cycle per iteration
+  hpmg       (--hlevels N, N != 0) the same with PMultigrid(pb, h_levels=N): h-levels under
+             degree 1; interleaved with the others window by window, whole solves alternating
+             with pmg's; --no-yardsticks leaves the two fused loops out
 
 Per-iteration time: device events between the steps of `iterate_timed(n)`, per
 window the mean of the first n - 1 steps, per variant the median over the
@@ -50,6 +54,10 @@ def main(argv=None) -> int:
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--max-iter", type=int, default=6000)
+    ap.add_argument("--hlevels", type=int, default=0,
+                    help="add the hpmg variant: PMultigrid(pb, h_levels=N) (-1: all)")
+    ap.add_argument("--no-yardsticks", action="store_true",
+                    help="leave out cg_fused and pcg_fused")
     a = ap.parse_args(argv)
 
     import torch
@@ -59,6 +67,7 @@ def main(argv=None) -> int:
     from benchmark_dolfinx_amd.models.poisson import PoissonProblem
     from benchmark_dolfinx_amd.parallel.comm import Comm
     from benchmark_dolfinx_amd.solvers.cg import DeviceCG
+    from benchmark_dolfinx_amd.solvers.pmg import PMultigrid
 
     if not torch.cuda.is_available():
         raise SystemExit("pmg_compare needs a GPU (no timing is taken without one)")
@@ -73,13 +82,17 @@ def main(argv=None) -> int:
             cg = DeviceCG(pb)
         elif variant == "pcg_fused":
             cg = DeviceCG(pb, "jacobi", loop="fused")
+        elif variant == "hpmg":
+            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels))
         else:
             cg = DeviceCG(pb, "pmg")
         x = pb.new_vector()
         cg.start(op, x, b)
         return op, cg, x
 
-    variants = ("cg_fused", "pcg_fused", "pmg")
+    variants = (() if a.no_yardsticks else ("cg_fused", "pcg_fused")) + ("pmg",) + (
+        ("hpmg",) if a.hlevels else ())
+    solves = tuple(v for v in variants if v.endswith("pmg"))
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
 
@@ -111,23 +124,24 @@ def main(argv=None) -> int:
                 break
         iters[v] = k if k < a.max_iter else None
 
-    # pmg: the whole solve, wall clock
-    wall = []
-    if iters["pmg"]:
-        op, cg, x = state["pmg"]
-        for _ in range(3):
+    # pmg (and hpmg): the whole solve, wall clock, the variants alternating
+    wall = {v: [] for v in solves if iters[v]}
+    true_res = {}
+    for _ in range(3):
+        for v in wall:
+            op, cg, x = state[v]
             x.zero_()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             cg.start(op, x, b)
-            cg.iterate(iters["pmg"])
+            cg.iterate(iters[v])
             torch.cuda.synchronize()
-            wall.append(time.perf_counter() - t0)
+            wall[v].append(time.perf_counter() - t0)
+    for v in wall:
+        op, cg, x = state[v]
         y = pb.new_vector()
         op.apply(x.clone(), y)
-        true_res = pb.norm(b - y) / pb.norm(b)
-    else:
-        true_res = None
+        true_res[v] = pb.norm(b - y) / pb.norm(b)
 
     # the V-cycle's parts, each alone
     def timed(fn):
@@ -165,6 +179,27 @@ def main(argv=None) -> int:
         nf_ = pb.lat.ndofs_local
         bw["prolong_tb_s"] = 8 * (nc_ + nf_) / (parts["prolong"] * 1e-3) / 1e12
         bw["restrict_kernel_tb_s"] = 8 * (nf_ + 2 * nc_) / (parts["restrict_kernel"] * 1e-3) / 1e12
+    hparts = None
+    if "hpmg" in state and state["hpmg"][1].pmg.h_levels:
+        # the degree-1 level and everything below it, without and with h-levels,
+        # and the first h-pair's transfer kernels alone
+        hp = state["hpmg"][1].pmg
+        i1 = len(hp.degrees) - 1
+        f1, c1 = hp.levels[i1], hp.levels[i1 + 1]
+        p1 = pmg.levels[i1]
+        if i1 > 0:
+            parts["degree1_level"] = timed(lambda: pmg._vcycle(i1, p1.r, p1.z))
+        hparts = {"cycle": timed(lambda: hp.apply(r, z)),
+                  "hrestrict_y": timed(lambda: f1.k.hrestrict(c1.latd, f1.H, f1.t, f1.y, c1.r)),
+                  "hprolong": timed(lambda: f1.k.hprolong(c1.latd, f1.H, c1.z, f1.t, False)),
+                  "hprolong_add": timed(lambda: f1.k.hprolong(c1.latd, f1.H, c1.z, f1.t, True))}
+        if i1 > 0:
+            hparts["degree1_and_h_levels"] = timed(lambda: hp._vcycle(i1, f1.r, f1.z))
+        n1, n2 = f1.pb.lat.ndofs_local, c1.pb.lat.ndofs_local
+        bw["hrestrict_y_tb_s"] = 8 * (2 * n1 + n2) / (hparts["hrestrict_y"] * 1e-3) / 1e12
+        bw["hprolong_tb_s"] = 8 * (n1 + n2) / (hparts["hprolong"] * 1e-3) / 1e12
+        bw["hprolong_add_tb_s"] = 8 * (2 * n1 + n2) / (hparts["hprolong_add"] * 1e-3) / 1e12
+        hparts["pair_dofs"] = [n1, n2]
     nown = pb.lat.ndofs_owned
     bw["cheb_step_tb_s"] = 8 * 7 * nown / (parts["cheb_step"] * 1e-3) / 1e12
     bw["cheb_step_first_tb_s"] = 8 * 4 * nown / (parts["cheb_step_first"] * 1e-3) / 1e12
@@ -177,16 +212,25 @@ def main(argv=None) -> int:
     stream_tbs = 3 * 8 * n / (stream_ms * 1e-3) / 1e12
 
     rec = {"degree": a.degree, "perturb": a.perturb, "kappa": a.kappa, "mesh": list(nx),
-           "ndofs": pb.ndofs_global, "kernel": state["cg_fused"][0].name,
+           "ndofs": pb.ndofs_global, "kernel": state["pmg"][0].name,
            "level_kernels": [getattr(v.op, "name", type(v.op).__name__) for v in pmg.levels],
            "pmg": pmg.info(), "ms_per_iter": ms, "tol": a.tol, "iters_to_tol": iters,
            "time_to_tol_s": {v: (iters[v] * ms[v]["median"] * 1e-3 if iters.get(v) else None)
                              for v in iters},
-           "pmg_wall_s": {"median": statistics.median(wall), "min": min(wall), "max": max(wall)}
-           if wall else None,
-           "pmg_true_residual": true_res, "cycle_parts_ms": parts, "bandwidth": bw,
+           "pmg_wall_s": {"median": statistics.median(wall["pmg"]), "min": min(wall["pmg"]),
+                          "max": max(wall["pmg"])} if "pmg" in wall else None,
+           "pmg_true_residual": true_res.get("pmg"), "cycle_parts_ms": parts, "bandwidth": bw,
            "stream_2r1w": {"ms": stream_ms, "tb_per_s": stream_tbs},
            "device": torch.cuda.get_device_name(0)}
+    if "hpmg" in state:
+        hp = state["hpmg"][1].pmg
+        rec["hpmg"] = hp.info()
+        rec["hpmg_level_kernels"] = [getattr(v.op, "name", type(v.op).__name__) for v in hp.levels]
+        rec["hpmg_wall_s"] = {"median": statistics.median(wall["hpmg"]), "min": min(wall["hpmg"]),
+                              "max": max(wall["hpmg"])} if "hpmg" in wall else None
+        rec["hpmg_true_residual"] = true_res.get("hpmg")
+        rec["hpmg_parts_ms"] = hparts
+        hp.close()
     pmg.close()
     for op, _, _ in state.values():
         op.close()
