@@ -15,7 +15,9 @@ fused,v1,dofmap}, --geometry {auto,otf,otf-general,stored}, --kappa {constant,ra
 (with --cg: CG preconditioned with the matrix-free operator diagonal, or with
 a p-multigrid V-cycle; --pmg_smooth N / --pmg_coarse N: Chebyshev degree of
 its smoothers / of its coarsest-level solve; --pmg_hlevels N: geometric
-h-levels under its degree-1 level, -1 = as many as the mesh allows),
+h-levels under its degree-1 level, -1 = as many as the mesh allows;
+--pmg_float {32,64}: precision of its V-cycle, 32 under --float 64 = the
+mixed-precision solve),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -86,6 +88,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pmg_hlevels", type=int, default=0,
                     help="Geometric h-levels under the p-multigrid's degree-1 level (--cg "
                          "--precond pmg): 0 = none, N = at most N, -1 = as many as the mesh allows")
+    ap.add_argument("--pmg_float", type=int, default=None, choices=[32, 64],
+                    help="Float size of the p-multigrid V-cycle (--cg --precond pmg; default: "
+                         "--float): 32 with --float 64 runs the FP32 cycle inside the FP64 CG")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -102,6 +107,10 @@ def parse_args(argv=None):
         raise SystemExit("error: Invalid float size. Must be 32 or 64.")
     if args.qmode > 1 or args.qmode < 0:
         raise SystemExit("error: Invalid qmode.")
+    if args.pmg_float is not None and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_float' needs 'cg' and 'precond pmg'")
+    if args.pmg_float is not None and args.pmg_float > args.float:
+        raise SystemExit("error: Option 'pmg_float' cannot exceed 'float'")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
@@ -205,12 +214,14 @@ def run_benchmark(comm, nx, args, platform):
     dtype = torch.float64 if args.float == 64 else torch.float32
     pb = PoissonProblem(comm, nx, args.degree, args.qmode, args.use_gauss, dtype,
                         platform, args.geom_perturb_fact, args.kappa)
+    pmg_opts = {"smooth_degree": args.pmg_smooth, "coarse_degree": args.pmg_coarse,
+                "h_levels": args.pmg_hlevels}
+    if args.pmg_float is not None:
+        pmg_opts["cycle_dtype"] = torch.float64 if args.pmg_float == 64 else torch.float32
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,
-                         pmg_opts={"smooth_degree": args.pmg_smooth,
-                                   "coarse_degree": args.pmg_coarse,
-                                   "h_levels": args.pmg_hlevels})
+                         pmg_opts=pmg_opts)
     t = res.mat_free_time
     gdofs = pb.ndofs_global * args.nreps / (1e9 * t) if t > 0 else 0.0
     out = {"ncells_global": pb.ncells_global, "ndofs_global": pb.ndofs_global,

@@ -10,22 +10,16 @@
 //   * x/r updates and the r.r reduction are one fused pass;
 //   * reductions and updates walk the owned sub-box of the local lattice
 //     one z-row per wave (rows are 128-byte aligned by the storage pitch).
-#include "bdx_common.h"
+#include "blas_rows.h"
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWaves = kBlock / 64;
-
-struct RowSpace {
-  int64_t L1, ld;       // storage strides
-  int64_t o0, o1, o2;   // owned extents
-};
-
-__device__ __forceinline__ int64_t row_base(const RowSpace& s, int64_t row) {
-  const int64_t i = row / s.o1, j = row - i * s.o1;
-  return (i * s.L1 + j) * s.ld;
-}
+// the row walk, and the loop bodies shared with mixed.hip
+using bdx_rows::grid_for_rows;
+using bdx_rows::kBlock;
+using bdx_rows::kWaves;
+using bdx_rows::row_base;
+using bdx_rows::RowSpace;
 
 // Fused dot-product kernel: per-block partial sums of a.b (deterministic order).
 template <typename T>
@@ -33,15 +27,7 @@ __global__ void __launch_bounds__(kBlock)
     dot_rows_kernel(RowSpace s, const T* __restrict__ a, const T* __restrict__ b,
                     double* __restrict__ partials) {
   __shared__ double lds[16];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  double acc = 0.0;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64)
-      acc += static_cast<double>(a[base + k]) * static_cast<double>(b[base + k]);
-  }
+  const double acc = bdx_rows::dot_rows<T, T>(s, a, b);
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
@@ -66,20 +52,7 @@ __global__ void __launch_bounds__(kBlock)
                      double* __restrict__ partials) {
   __shared__ double lds[16];
   const T alpha = static_cast<T>(scal[rn_slot] / scal[pap_slot]);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  double acc = 0.0;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) {
-      const int64_t i = base + k;
-      x[i] = x[i] + alpha * p[i];
-      const T rn = r[i] - alpha * y[i];
-      r[i] = rn;
-      acc += static_cast<double>(rn) * static_cast<double>(rn);
-    }
-  }
+  const double acc = bdx_rows::cg_update_rows<T, false>(s, alpha, x, r, p, y, nullptr);
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
@@ -90,13 +63,7 @@ __global__ void __launch_bounds__(kBlock)
     p_update_kernel(RowSpace s, T* __restrict__ p, const T* __restrict__ r,
                     const double* __restrict__ scal, int num, int den) {
   const T beta = static_cast<T>(scal[num] / scal[den]);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) p[base + k] = beta * p[base + k] + r[base + k];
-  }
+  bdx_rows::p_update_rows<T, T>(s, beta, p, r);
 }
 
 // Jacobi-preconditioned CG (z = dinv . r is never stored):
@@ -344,11 +311,6 @@ int box_copy_vi(int mode, T* vec, VecIdx vi, const int64_t* boxes, int nboxes, i
       box_copy_kernel<T, 2><<<g, kBlock, 0, st>>>(vec, vi, boxes, nboxes, total, buf, b);
   }
   return static_cast<int>(hipGetLastError());
-}
-
-int grid_for_rows(int64_t nrows) {
-  const int64_t want = (nrows + kWaves - 1) / kWaves;
-  return static_cast<int>(want < 2048 ? (want > 0 ? want : 1) : 2048);
 }
 
 }  // namespace

@@ -1067,6 +1067,19 @@ void cheb_step_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, 
     }
 }
 
+// out = (TO)a over the owned rows: the precision boundary of the mixed
+// multigrid solve (csrc/hip/mixed.hip); nothing outside the rows is touched.
+template <typename TI, typename TO>
+void convert_rows_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, const TI* a,
+                       TO* out) {
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t i = 0; i < o0; ++i)
+    for (int64_t j = 0; j < o1; ++j) {
+      const int64_t base = (i * L1 + j) * ld;
+      for (int64_t k = base; k < base + o2; ++k) out[k] = static_cast<TO>(a[k]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1267,6 +1280,20 @@ int bdx_host_version() { return 1; }
 
 BDX_HOST_API(double, f64)
 BDX_HOST_API(float, f32)
+
+// out = (float)a over the owned rows (round to nearest even): the host twin
+// of bdx_demote_f64_f32 (csrc/hip/mixed.hip).
+void bdx_cpu_demote_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,
+                            const double* a, float* out) {
+  convert_rows_host<double, float>(L1, ld, o0, o1, o2, a, out);
+}
+
+// out = (double)a over the owned rows (exact): the host twin of
+// bdx_promote_f32_f64.
+void bdx_cpu_promote_f32_f64(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,
+                             const float* a, double* out) {
+  convert_rows_host<float, double>(L1, ld, o0, o1, o2, a, out);
+}
 
 // CPU unit test of the RCCL deadline policy (csrc/include/bdx_watchdog.h, used
 // by the native runtime around every blocking RCCL call and host wait): a

@@ -83,6 +83,13 @@ def declare(lib) -> None:
                 _d(lib, f"bdx_fused5_tables_{suf}_p{P}", [i32, i32, vp, vp, vp, vp])
                 _d(lib, f"bdx_fused5_tile_p{P}_{suf}", [i32, vp, vp])
                 _d(lib, f"bdx_fused5_segments_{suf}_p{P}", [i32, i32, i32])
+    # FP64 CG around an FP32 multigrid cycle (mixed.hip)
+    _d(lib, "bdx_demote_f64_f32", [i64, i64, i64, i64, i64, vp, vp, vp])
+    _d(lib, "bdx_promote_f32_f64", [i64, i64, i64, i64, i64, vp, vp, vp])
+    _d(lib, "bdx_cg_update_demote_f64",
+       [i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp])
+    _d(lib, "bdx_dot_f64_f32", [i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp])
+    _d(lib, "bdx_p_update_f64_f32", [i64, i64, i64, i64, i64, vp, vp, vp, i32, i32, vp])
     _d(lib, "bdx_fused_tile", [i32, vp, vp])
     # native CG runtime (runtime.hip)
     _d(lib, "bdx_rt_nccl_unique_id", [vp])

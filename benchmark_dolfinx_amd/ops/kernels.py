@@ -258,6 +258,44 @@ class HipKernels:
                                         ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc), _stream()),
                "hrestrict")
 
+    # ------------------------------------- FP64 CG around an FP32 cycle
+    def _rows(self, v64=(), v32=()):
+        """The row-walk arguments, after checking that the float64 and
+        float32 vectors are lattice vectors of those types (the kernels index
+        both with one offset)."""
+        for vs, dt in ((v64, torch.float64), (v32, torch.float32)):
+            for v in vs:
+                if v.dtype != dt or tuple(v.shape) != tuple(self.lat.shape):
+                    raise TypeError(f"expected a {dt} lattice vector of shape "
+                                    f"{tuple(self.lat.shape)}, got {v.dtype} {tuple(v.shape)}")
+        return self.lat.L[1], self.lat.ld, self.o[0], self.o[1], self.o[2]
+
+    def demote(self, a, out):
+        """out (float32) = a (float64) over the owned rows, round to nearest even."""
+        _check(self.lib.bdx_demote_f64_f32(*self._rows((a,), (out,)), ptr(a), ptr(out), _stream()), "demote")
+
+    def promote(self, a, out):
+        """out (float64) = a (float32) over the owned rows (exact)."""
+        _check(self.lib.bdx_promote_f32_f64(*self._rows((out,), (a,)), ptr(a), ptr(out), _stream()), "promote")
+
+    def cg_update_demote(self, x, r, p, y, scal, rn_slot, pap_slot, out_slot, partials, r32):
+        """`cg_update` in float64 that also stores r32 = (float32) r."""
+        _check(self.lib.bdx_cg_update_demote_f64(*self._rows((x, r, p, y), (r32,)), ptr(x), ptr(r),
+                                                 ptr(p), ptr(y),
+                                                 ptr(scal), rn_slot, pap_slot, out_slot,
+                                                 ptr(partials), ptr(r32), _stream()),
+               "cg_update_demote")
+
+    def dot_f64_f32(self, a, b32, partials, out, slot: int):
+        """out[slot] = sum a (float64) . b32 (float32), b32 promoted in registers."""
+        _check(self.lib.bdx_dot_f64_f32(*self._rows((a,), (b32,)), ptr(a), ptr(b32), ptr(partials),
+                                        ptr(out), slot, _stream()), "dot_f64_f32")
+
+    def p_update_f64_f32(self, p, z32, scal, num, den):
+        """p (float64) = (s[num] / s[den]) p + z32 (float32)."""
+        _check(self.lib.bdx_p_update_f64_f32(*self._rows((p,), (z32,)), ptr(p), ptr(z32), ptr(scal),
+                                             num, den, _stream()), "p_update_f64_f32")
+
     def box_copy(self, mode: int, vec, lat, side, buf):
         _check(self._f("bdx_box_copy")(mode, ptr(vec), lat.L[1], lat.ld, ptr(side.table),
                                        len(side.boxes), side.total, ptr(buf), _stream()),
@@ -307,6 +345,23 @@ class HostKernels:
         if self._f("bdx_cpu_hrestrict")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
                                         ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc)):
             raise ValueError("hrestrict: not a pair of degree-1 lattices of one partition")
+
+    def _rows(self, a, da, out, do):
+        for v, dt in ((a, da), (out, do)):
+            if v.dtype != dt or tuple(v.shape) != tuple(self.lat.shape):
+                raise TypeError(f"expected a {dt} lattice vector of shape "
+                                f"{tuple(self.lat.shape)}, got {v.dtype} {tuple(v.shape)}")
+        return self.lat.L[1], self.lat.ld, self.o[0], self.o[1], self.o[2]
+
+    def demote(self, a, out):
+        """out (float32) = a (float64) over the owned rows, round to nearest even."""
+        self.lib.bdx_cpu_demote_f64_f32(*self._rows(a, torch.float64, out, torch.float32),
+                                        ptr(a), ptr(out))
+
+    def promote(self, a, out):
+        """out (float64) = a (float32) over the owned rows (exact)."""
+        self.lib.bdx_cpu_promote_f32_f64(*self._rows(a, torch.float32, out, torch.float64),
+                                         ptr(a), ptr(out))
 
     def axpy(self, out, alpha: float, x, y):
         o = self.o

@@ -86,6 +86,9 @@ def host():
                 _declare(lib, f"bdx_cpu_hrestrict_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp], i32)
                 _declare(lib, f"bdx_cpu_cheb_step_{suf}",
                          [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
+            # the precision boundary of the mixed multigrid solve
+            _declare(lib, "bdx_cpu_demote_f64_f32", [i64, i64, i64, i64, i64, vp, vp])
+            _declare(lib, "bdx_cpu_promote_f32_f64", [i64, i64, i64, i64, i64, vp, vp])
             _host = lib
     return _host
 

@@ -139,7 +139,14 @@ class DeviceCG:
     precond="pmg": CG preconditioned with a p-multigrid V-cycle (`pmg`: a
     `PMultigrid` of the problem; None builds the default one).  Generic loop
     only, composed of existing kernels: op.apply, dot, cg_update (r.r into
-    RNORM), `pmg.apply(r, z)` with z stored here, dot(r, z), p_update."""
+    RNORM), `pmg.apply(r, z)` with z stored here, dot(r, z), p_update.
+
+    With a mixed-precision `pmg` (`pmg.mixed`: FP32 cycle, FP64 problem) the
+    boundary between the precisions is fused into the loop's own passes
+    (csrc/hip/mixed.hip): cg_update_demote also stores the residual as FP32
+    into `pmg.rc`, `pmg.apply_cycle(pmg.rc, pmg.zc)` runs the raw cycle, and
+    dot_f64_f32 / p_update_f64_f32 read the FP32 `pmg.zc`, so no FP64 z is
+    allocated."""
 
     # float64 scalar slots
     RR0, RR1, PAP = 0, 1, 2
@@ -176,7 +183,9 @@ class DeviceCG:
         self.partials = torch.zeros(self.k.npart, dtype=torch.float64, device=dev)
         self.r = pb.new_vector()
         self.y = pb.new_vector()
-        if self.pmg is not None:
+        # FP32 cycle under this FP64 loop: z lives in the preconditioner (pmg.zc)
+        self.mixed = self.pmg is not None and bool(getattr(self.pmg, "mixed", False))
+        if self.pmg is not None and not self.mixed:
             self.z = pb.new_vector()
         # the fused loop keeps its search directions in the operator
         self.p = pb.new_vector() if loop == "generic" else None
@@ -204,6 +213,19 @@ class DeviceCG:
                 raise ValueError(f"operator {name!r} has no fused preconditioned CG loop "
                                  "(fused2, fused3 and fused5 do); use loop='generic'")
             op.cg_start(self, x, b)
+            return
+        if self.mixed:
+            # the same prologue with z0 kept in FP32 (pmg.zc) and promoted into p0
+            pmg = self.pmg
+            op.apply(x, y)
+            k.axpy(r, -1.0, y, b)
+            k.demote(r, pmg.rc)
+            pmg.apply_cycle(pmg.rc, pmg.zc)
+            k.promote(pmg.zc, p)
+            k.dot_f64_f32(r, pmg.zc, self.partials, scal, self.RR0)
+            self._allreduce(self.RR0)
+            k.dot(r, r, self.partials, scal, self.RNORM)
+            self._allreduce(self.RNORM)
             return
         if self.pmg is not None:
             # r0 = b - A x0, z0 = M^-1 r0, p0 = z0, rz0 = r0.z0, rr0 = r0.r0
@@ -245,6 +267,23 @@ class DeviceCG:
         k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
         if self.fused_pcg:
             op.cg_iterate(self, n, flush=flush)
+            return
+        if self.mixed:
+            pmg = self.pmg
+            for _ in range(n):
+                cur = self.RR0 if self.it % 2 == 0 else self.RR1
+                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
+                op.apply(p, y)
+                k.dot(p, y, self.partials, scal, self.PAP)
+                self._allreduce(self.PAP)
+                k.cg_update_demote(x, r, p, y, scal, cur, self.PAP, self.RNORM, self.partials,
+                                   pmg.rc)
+                self._allreduce(self.RNORM)
+                pmg.apply_cycle(pmg.rc, pmg.zc)
+                k.dot_f64_f32(r, pmg.zc, self.partials, scal, nxt)
+                self._allreduce(nxt)
+                k.p_update_f64_f32(p, pmg.zc, scal, nxt, cur)
+                self.it += 1
             return
         if self.pmg is not None:
             z = self.z

@@ -34,6 +34,15 @@ smoothed level.  Between two degree-1 levels the transfers are trilinear in
 index space (csrc/hip/lap_htransfer.h) and fold the cycle's two vector passes:
 r_c = R (r - A z) in the restriction's load, z += P z_c in the prolongation's
 store.  The exchange protocol around them is that of the p-transfers.
+
+Mixed precision (`cycle_dtype=torch.float32` on an FP64 problem, off by
+default): every level, level 0 and the h-levels included, is an FP32 problem
+with the FP64 problem's comm, cells, partition, perturbation, coefficient and
+shear, and the whole setup and cycle above run on them unchanged.  `apply`
+keeps its FP64 contract by demoting r into `rc`, running `apply_cycle(rc, zc)`
+and promoting `zc` (csrc/hip/mixed.hip, host twins in csrc/host/bdx_host.cpp);
+a caller that fuses the boundary into its own kernels (`DeviceCG`) calls
+`apply_cycle` directly.  The cycle is linear in r and is applied unscaled.
 """
 
 from __future__ import annotations
@@ -101,26 +110,39 @@ class PMultigrid:
     h_levels: 0 = the p-levels only; N > 0 = at most N geometric h-levels
     under degree 1; -1 = as many as `fem.mesh.h_hierarchy` allows.  `h_levels`
     then holds the number built and `h_cells` their global cell counts; the
-    hierarchy depends on the partition's cut points (fem/mesh.py)."""
+    hierarchy depends on the partition's cut points (fem/mesh.py).
+
+    cycle_dtype: None or the problem's dtype = the hierarchy in the problem's
+    precision, level 0 being `pb` itself; torch.float32 on a float64 problem =
+    the mixed mode of the module docstring (`mixed` is then True, `rc` / `zc`
+    are the FP32 level-0 work vectors and `info()` carries `cycle_float`)."""
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
-                 h_levels: int = 0):
+                 h_levels: int = 0, cycle_dtype: torch.dtype | None = None):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
             raise ValueError("smoother ranges must exceed 1")
         if isinstance(h_levels, bool) or not isinstance(h_levels, (int, np.integer)) or h_levels < -1:
             raise ValueError("h_levels must be -1 (all), 0 (none) or a positive count")
+        if cycle_dtype is None:
+            cycle_dtype = pb.dtype
+        if cycle_dtype not in (torch.float32, torch.float64) or \
+                (cycle_dtype == torch.float64 and pb.dtype != torch.float64):
+            raise ValueError(f"cycle_dtype must be None, the problem's {pb.dtype} or, on a "
+                             f"float64 problem, torch.float32; got {cycle_dtype!r}")
         self.pb = pb
+        self.cycle_dtype = cycle_dtype
+        self.mixed = cycle_dtype != pb.dtype    # FP32 cycle under an FP64 problem
         self.smooth_degree, self.smooth_range = int(smooth_degree), float(smooth_range)
         self.coarse_degree, self.coarse_range = int(coarse_degree), float(coarse_range)
         self.degrees = level_degrees(pb.degree)
         self.levels: list[_Level] = []
         ncells = pb.lat.ncells_global
         for i, P in enumerate(self.degrees):
-            lpb = pb if i == 0 else PoissonProblem(
-                pb.comm, ncells, P, pb.qmode, pb.use_gauss, pb.dtype, pb.platform,
+            lpb = pb if i == 0 and not self.mixed else PoissonProblem(
+                pb.comm, ncells, P, pb.qmode, pb.use_gauss, cycle_dtype, pb.platform,
                 pb.perturb, pb.coefficient, shear=pb.shear, partition=pb.partition)
             lv = _Level(lpb)
             if i > 0:
@@ -135,7 +157,7 @@ class PMultigrid:
                 above = self.levels[-1]
                 lv = _Level(PoissonProblem.coarsened(above.pb, lat, fpos))
                 lv.r, lv.z = lv.pb.new_vector(), lv.pb.new_vector()
-                above.H = HTransferTables(fpos, pb.dtype, pb.device)
+                above.H = HTransferTables(fpos, cycle_dtype, pb.device)
                 self.levels.append(lv)
                 self.h_cells.append(tuple(int(c) for c in lat.ncells_global))
         self.h_levels_requested = int(h_levels)
@@ -154,6 +176,10 @@ class PMultigrid:
                 lv.coef = chebyshev_coefficients(1.1 * lv.lambda_max, self.smooth_range,
                                                  self.smooth_degree)
         self.lambda_max = [lv.lambda_max for lv in self.levels]
+        # mixed mode: the level-0 residual and correction at cycle precision
+        self.rc = self.zc = None
+        if self.mixed:
+            self.rc, self.zc = self.levels[0].pb.new_vector(), self.levels[0].pb.new_vector()
 
     # ---------------------------------------------------------------- setup
     @staticmethod
@@ -245,7 +271,18 @@ class PMultigrid:
     def apply(self, r: torch.Tensor, z: torch.Tensor) -> None:
         """z = M^-1 r (lattice-shaped; the owned entries are valid).  r is not
         modified; it must vanish on Dirichlet dofs, as every CG residual does."""
-        self._vcycle(0, r, z)
+        if not self.mixed:
+            self._vcycle(0, r, z)
+            return
+        k = self.levels[0].k
+        k.demote(r, self.rc)
+        self._vcycle(0, self.rc, self.zc)
+        k.promote(self.zc, z)
+
+    def apply_cycle(self, rc: torch.Tensor, zc: torch.Tensor) -> None:
+        """The raw V-cycle zc = M^-1 rc on level-0 vectors of the cycle
+        precision (`apply` without the demotion and promotion of mixed mode)."""
+        self._vcycle(0, rc, zc)
 
     def info(self) -> dict:
         out = {"degrees": list(self.degrees), "lambda_max": list(self.lambda_max),
@@ -253,6 +290,8 @@ class PMultigrid:
         if self.h_levels_requested != 0:
             out["h_levels"] = self.h_levels
             out["h_cells"] = [list(c) for c in self.h_cells]
+        if self.mixed:
+            out["cycle_float"] = 32
         return out
 
     def close(self) -> None:

@@ -5,6 +5,8 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
   python scripts/pmg_compare.py --degree 3 --perturb 0.2 --kappa random [--ndofs 20000000]
   python scripts/pmg_compare.py --degree 6 --perturb 0.0 --kappa constant
   python scripts/pmg_compare.py --degree 3 --hlevels -1      (adds the hpmg column, profiles/hpmg.md)
+  python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --tol2 1e-12 --no-yardsticks
+                                                             (FP32 cycles, profiles/pmg_mixed.md)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -15,6 +17,10 @@ its own auto-selected operator:
   hpmg       (--hlevels N, N != 0) the same with PMultigrid(pb, h_levels=N): h-levels under
              degree 1; interleaved with the others window by window, whole solves alternating
              with pmg's; --no-yardsticks leaves the two fused loops out
+  pmg32      (--cycle_float 32) pmg with PMultigrid(pb, cycle_dtype=float32): the FP32 V-cycle
+  hpmg32     inside the FP64 loop, and the same for hpmg; interleaved like hpmg.  --tol2 T also
+             counts and times every pmg variant's solve to the second tolerance T, and the five
+             kernels of the precision boundary (csrc/hip/mixed.hip) are timed alone
 
 Per-iteration time: device events between the steps of `iterate_timed(n)`, per
 window the mean of the first n - 1 steps, per variant the median over the
@@ -56,6 +62,10 @@ def main(argv=None) -> int:
     ap.add_argument("--max-iter", type=int, default=6000)
     ap.add_argument("--hlevels", type=int, default=0,
                     help="add the hpmg variant: PMultigrid(pb, h_levels=N) (-1: all)")
+    ap.add_argument("--cycle_float", type=int, default=64, choices=[32, 64],
+                    help="32: add pmg32 (and, with --hlevels, hpmg32), the FP32 V-cycle in FP64 CG")
+    ap.add_argument("--tol2", type=float, default=0.0,
+                    help="a second, tighter tolerance for the pmg variants' solves (0: none)")
     ap.add_argument("--no-yardsticks", action="store_true",
                     help="leave out cg_fused and pcg_fused")
     a = ap.parse_args(argv)
@@ -84,6 +94,11 @@ def main(argv=None) -> int:
             cg = DeviceCG(pb, "jacobi", loop="fused")
         elif variant == "hpmg":
             cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels))
+        elif variant == "pmg32":
+            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, cycle_dtype=torch.float32))
+        elif variant == "hpmg32":
+            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels,
+                                                    cycle_dtype=torch.float32))
         else:
             cg = DeviceCG(pb, "pmg")
         x = pb.new_vector()
@@ -92,7 +107,9 @@ def main(argv=None) -> int:
 
     variants = (() if a.no_yardsticks else ("cg_fused", "pcg_fused")) + ("pmg",) + (
         ("hpmg",) if a.hlevels else ())
-    solves = tuple(v for v in variants if v.endswith("pmg"))
+    if a.cycle_float == 32:
+        variants += ("pmg32",) + (("hpmg32",) if a.hlevels else ())
+    solves = tuple(v for v in variants if "pmg" in v)
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
 
@@ -111,7 +128,7 @@ def main(argv=None) -> int:
     ms = {v: {"median": statistics.median(s), "min": min(s), "max": max(s)}
           for v, s in samples.items()}
 
-    iters = {}
+    iters, iters2 = {}, {}
     for v in variants:
         op, cg, x = state[v]
         cg.start(op, x.zero_(), b)
@@ -123,6 +140,11 @@ def main(argv=None) -> int:
             if cg.residual_norm2() < a.tol * a.tol * rr0:
                 break
         iters[v] = k if k < a.max_iter else None
+        if a.tol2 > 0 and v in solves and iters[v]:
+            while k < a.max_iter and cg.residual_norm2() >= a.tol2 * a.tol2 * rr0:
+                cg.iterate(1)
+                k += 1
+            iters2[v] = k if k < a.max_iter else None
 
     # pmg (and hpmg): the whole solve, wall clock, the variants alternating
     wall = {v: [] for v in solves if iters[v]}
@@ -142,6 +164,24 @@ def main(argv=None) -> int:
         y = pb.new_vector()
         op.apply(x.clone(), y)
         true_res[v] = pb.norm(b - y) / pb.norm(b)
+    # the same to the second tolerance
+    wall2 = {v: [] for v in solves if iters2.get(v)}
+    true_res2 = {}
+    for _ in range(3):
+        for v in wall2:
+            op, cg, x = state[v]
+            x.zero_()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            cg.start(op, x, b)
+            cg.iterate(iters2[v])
+            torch.cuda.synchronize()
+            wall2[v].append(time.perf_counter() - t0)
+    for v in wall2:
+        op, cg, x = state[v]
+        y = pb.new_vector()
+        op.apply(x.clone(), y)
+        true_res2[v] = pb.norm(b - y) / pb.norm(b)
 
     # the V-cycle's parts, each alone
     def timed(fn):
@@ -222,6 +262,49 @@ def main(argv=None) -> int:
            "pmg_true_residual": true_res.get("pmg"), "cycle_parts_ms": parts, "bandwidth": bw,
            "stream_2r1w": {"ms": stream_ms, "tb_per_s": stream_tbs},
            "device": torch.cuda.get_device_name(0)}
+    def spread(s):
+        return {"median": statistics.median(s), "min": min(s), "max": max(s)}
+
+    if a.tol2 > 0:
+        rec["tol2"] = {"tol": a.tol2, "iters": iters2, "true_residual": true_res2,
+                       "wall_s": {v: spread(s) for v, s in wall2.items()}}
+    if a.cycle_float == 32:
+        # the mixed variants, and the kernels of the precision boundary alone:
+        # bytes per owned dof a kernel must move (f64 8, f32 4)
+        cg32 = state["pmg32"][1]
+        m32 = cg32.pmg
+        k, p_, y_ = pb.kernels, cg32.p, cg32.y
+        scal = torch.ones(8, dtype=torch.float64, device="cuda")
+        xs = pb.new_vector()
+        kern = {
+            "demote": (12, lambda: k.demote(r, m32.rc)),
+            "promote": (12, lambda: k.promote(m32.zc, z)),
+            "cg_update_demote": (52, lambda: k.cg_update_demote(xs, r, p_, y_, scal, 0, 1, 5,
+                                                                cg32.partials, m32.rc)),
+            "cg_update": (48, lambda: k.cg_update(xs, r, p_, y_, scal, 0, 1, 5, cg32.partials)),
+            "dot_f64_f32": (12, lambda: k.dot_f64_f32(r, m32.zc, cg32.partials, scal, 5)),
+            "dot": (16, lambda: k.dot(r, z, cg32.partials, scal, 5)),
+            "p_update_f64_f32": (20, lambda: k.p_update_f64_f32(p_, m32.zc, scal, 6, 7)),
+            "p_update": (24, lambda: k.p_update(p_, z, scal, 6, 7)),
+        }
+        mk = {}
+        for name, (nbytes, fn) in kern.items():
+            t = timed(fn)
+            mk[name] = {"ms": t, "bytes_per_dof": nbytes,
+                        "tb_per_s": nbytes * nown / (t * 1e-3) / 1e12}
+        rec["mixed"] = {"pmg32": m32.info(), "kernels": mk,
+                        "cycle_ms": {"pmg": parts["cycle"],
+                                     "pmg32": timed(lambda: m32.apply_cycle(m32.rc, m32.zc))},
+                        "wall_s": {v: spread(wall[v]) for v in ("pmg32", "hpmg32") if v in wall},
+                        "true_residual": {v: true_res[v] for v in ("pmg32", "hpmg32")
+                                          if v in true_res}}
+        if "hpmg32" in state:
+            h32 = state["hpmg32"][1].pmg
+            rec["mixed"]["hpmg32"] = h32.info()
+            rec["mixed"]["cycle_ms"]["hpmg"] = hparts["cycle"] if hparts else None
+            rec["mixed"]["cycle_ms"]["hpmg32"] = timed(lambda: h32.apply_cycle(h32.rc, h32.zc))
+            h32.close()
+        m32.close()
     if "hpmg" in state:
         hp = state["hpmg"][1].pmg
         rec["hpmg"] = hp.info()
