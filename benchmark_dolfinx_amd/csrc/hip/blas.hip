@@ -9,28 +9,21 @@
 //   * the CG scalars (alpha, beta) are formed on the device from those slots;
 //   * x/r updates and the r.r reduction are one fused pass;
 //   * reductions and updates walk the owned sub-box of the local lattice
-//     one z-row per wave (rows are 128-byte aligned by the storage pitch).
+//     one z-row per wave (rows are 128-byte aligned by the storage pitch):
+//     `for_each_owned` of blas_rows.h, which also holds the dot, cg_update and
+//     p_update kernels (instantiated here and, with an FP32 operand, in
+//     mixed.hip).
 #include "blas_rows.h"
 
 namespace {
 
-// the row walk, and the loop bodies shared with mixed.hip
+using bdx_rows::cg_update_kernel;
+using bdx_rows::dot_rows_kernel;
+using bdx_rows::for_each_owned;
 using bdx_rows::grid_for_rows;
 using bdx_rows::kBlock;
-using bdx_rows::kWaves;
-using bdx_rows::row_base;
+using bdx_rows::p_update_kernel;
 using bdx_rows::RowSpace;
-
-// Fused dot-product kernel: per-block partial sums of a.b (deterministic order).
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    dot_rows_kernel(RowSpace s, const T* __restrict__ a, const T* __restrict__ b,
-                    double* __restrict__ partials) {
-  __shared__ double lds[16];
-  const double acc = bdx_rows::dot_rows<T, T>(s, a, b);
-  const double t = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
 
 // Fixed-order sum of partials into out[slot] (single block).
 __global__ void __launch_bounds__(kBlock)
@@ -41,29 +34,6 @@ __global__ void __launch_bounds__(kBlock)
   for (int i = threadIdx.x; i < n; i += blockDim.x) acc += partials[i];
   const double t = block_sum(acc, lds);
   if (threadIdx.x == 0) out[slot] = t;
-}
-
-// CG: alpha = s[rn] / s[pap];  x += alpha p;  r -= alpha y;  partial r.r
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    cg_update_kernel(RowSpace s, T* __restrict__ x, T* __restrict__ r,
-                     const T* __restrict__ p, const T* __restrict__ y,
-                     const double* __restrict__ scal, int rn_slot, int pap_slot,
-                     double* __restrict__ partials) {
-  __shared__ double lds[16];
-  const T alpha = static_cast<T>(scal[rn_slot] / scal[pap_slot]);
-  const double acc = bdx_rows::cg_update_rows<T, false>(s, alpha, x, r, p, y, nullptr);
-  const double t = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// p = beta p + r with beta = s[num] / s[den] (owned rows).
-template <typename T>
-__global__ void __launch_bounds__(kBlock)
-    p_update_kernel(RowSpace s, T* __restrict__ p, const T* __restrict__ r,
-                    const double* __restrict__ scal, int num, int den) {
-  const T beta = static_cast<T>(scal[num] / scal[den]);
-  bdx_rows::p_update_rows<T, T>(s, beta, p, r);
 }
 
 // Jacobi-preconditioned CG (z = dinv . r is never stored):
@@ -77,22 +47,15 @@ __global__ void __launch_bounds__(kBlock)
                       int pap_slot, double* __restrict__ partials) {
   __shared__ double lds_rz[16], lds_rr[16];
   const T alpha = static_cast<T>(scal[rz_slot] / scal[pap_slot]);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
   double acc_rz = 0.0, acc_rr = 0.0;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) {
-      const int64_t i = base + k;
-      x[i] = x[i] + alpha * p[i];
-      const T rn = r[i] - alpha * y[i];
-      r[i] = rn;
-      const double rr = static_cast<double>(rn) * static_cast<double>(rn);
-      acc_rr += rr;
-      acc_rz += static_cast<double>(dinv[i]) * rr;
-    }
-  }
+  for_each_owned(s, [&](int64_t i) {
+    x[i] = x[i] + alpha * p[i];
+    const T rn = r[i] - alpha * y[i];
+    r[i] = rn;
+    const double rr = static_cast<double>(rn) * static_cast<double>(rn);
+    acc_rr += rr;
+    acc_rz += static_cast<double>(dinv[i]) * rr;
+  });
   const double tz = block_sum(acc_rz, lds_rz);
   const double tr = block_sum(acc_rr, lds_rr);
   if (threadIdx.x == 0) {
@@ -108,14 +71,7 @@ __global__ void __launch_bounds__(kBlock)
                         const T* __restrict__ dinv, const double* __restrict__ scal, int num,
                         int den) {
   const T beta = static_cast<T>(scal[num] / scal[den]);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64)
-      p[base + k] = beta * p[base + k] + dinv[base + k] * r[base + k];
-  }
+  for_each_owned(s, [&](int64_t i) { p[i] = beta * p[i] + dinv[i] * r[i]; });
 }
 
 // One step of the Chebyshev-Jacobi smoother (solvers/pmg.py) over the owned
@@ -126,24 +82,17 @@ template <typename T, bool FIRST>
 __global__ void __launch_bounds__(kBlock)
     cheb_step_kernel(RowSpace s, T a, T b, const T* __restrict__ dinv, const T* __restrict__ r,
                      const T* __restrict__ y, T* __restrict__ d, T* __restrict__ z) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) {
-      const int64_t i = base + k;
-      if constexpr (FIRST) {
-        const T dn = b * dinv[i] * r[i];
-        d[i] = dn;
-        z[i] = dn;
-      } else {
-        const T dn = a * d[i] + b * dinv[i] * (r[i] - y[i]);
-        d[i] = dn;
-        z[i] = z[i] + dn;
-      }
+  for_each_owned(s, [&](int64_t i) {
+    if constexpr (FIRST) {
+      const T dn = b * dinv[i] * r[i];
+      d[i] = dn;
+      z[i] = dn;
+    } else {
+      const T dn = a * d[i] + b * dinv[i] * (r[i] - y[i]);
+      d[i] = dn;
+      z[i] = z[i] + dn;
     }
-  }
+  });
 }
 
 // out = alpha x + y over owned rows (reference axpy, src/vector.hpp:228-240).
@@ -151,13 +100,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlock)
     axpy_kernel(RowSpace s, T* __restrict__ out, T alpha, const T* __restrict__ x,
                 const T* __restrict__ y) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) out[base + k] = alpha * x[base + k] + y[base + k];
-  }
+  for_each_owned(s, [&](int64_t i) { out[i] = alpha * x[i] + y[i]; });
 }
 
 // ------------------------------------------------------------- halo boxes
@@ -332,7 +275,7 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
                     int slot, hipStream_t st) {                               \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
-    dot_rows_kernel<T><<<g, kBlock, 0, st>>>(s, a, b, partials);              \
+    dot_rows_kernel<T, T><<<g, kBlock, 0, st>>>(s, a, b, partials);           \
     reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials, g, out, slot);     \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
@@ -342,8 +285,8 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
                           int out_slot, double* partials, hipStream_t st) {   \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
-    cg_update_kernel<T><<<g, kBlock, 0, st>>>(s, x, r, p, y, scal, rn_slot,   \
-                                              pap_slot, partials);            \
+    cg_update_kernel<T, false><<<g, kBlock, 0, st>>>(                         \
+        s, x, r, p, y, scal, rn_slot, pap_slot, partials, nullptr);           \
     reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials, g, scal, out_slot); \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
@@ -351,9 +294,8 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
                          int64_t o2, T* p, const T* r, const double* scal,    \
                          int num, int den, hipStream_t st) {                  \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
-    p_update_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(s, p, r,    \
-                                                                  scal, num,  \
-                                                                  den);       \
+    p_update_kernel<T, T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(         \
+        s, p, r, scal, num, den);                                             \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
   /* Jacobi PCG update: r.z -> scal[out_slot], r.r -> scal[rr_slot] */        \

@@ -11,67 +11,25 @@
 // Every kernel walks the owned sub-box one z-row per wave like blas.hip and
 // touches no entry outside it; the storage pitch is 16 elements in both
 // precisions, so one index serves both vectors of a node.  The three fused
-// kernels instantiate the loop bodies of blas.hip's kernels (blas_rows.h) and
-// reduce with its final pass, so they reproduce the composition of the
-// existing kernels bit for bit.
+// entry points launch further instances of the kernel templates that blas.hip
+// instantiates (blas_rows.h: cg_update_kernel<double, true>,
+// dot_rows_kernel<double, float>, p_update_kernel<double, float>) and reduce
+// with its final pass, so they reproduce the composition of the existing
+// kernels bit for bit.
 #include "blas_rows.h"
-
-// blas.hip: fixed-order sum of n per-block partials into out[slot]
-extern "C" int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
-                                   hipStream_t st);
 
 namespace {
 
+using bdx_rows::for_each_owned;
 using bdx_rows::grid_for_rows;
 using bdx_rows::kBlock;
-using bdx_rows::kWaves;
-using bdx_rows::row_base;
 using bdx_rows::RowSpace;
 
 // out = (TO)a over the owned rows.
 template <typename TI, typename TO>
 __global__ void __launch_bounds__(kBlock)
     convert_rows_kernel(RowSpace s, const TI* __restrict__ a, TO* __restrict__ out) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int64_t nrows = s.o0 * s.o1;
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wid; row < nrows;
-       row += static_cast<int64_t>(gridDim.x) * kWaves) {
-    const int64_t base = row_base(s, row);
-    for (int64_t k = lane; k < s.o2; k += 64) out[base + k] = static_cast<TO>(a[base + k]);
-  }
-}
-
-// cg_update_kernel<double> of blas.hip (same body), the new residual also
-// stored as float in r32.
-__global__ void __launch_bounds__(kBlock)
-    cg_update_demote_kernel(RowSpace s, double* __restrict__ x, double* __restrict__ r,
-                            const double* __restrict__ p, const double* __restrict__ y,
-                            const double* __restrict__ scal, int rn_slot, int pap_slot,
-                            double* __restrict__ partials, float* __restrict__ r32) {
-  __shared__ double lds[16];
-  const double alpha = scal[rn_slot] / scal[pap_slot];
-  const double acc = bdx_rows::cg_update_rows<double, true>(s, alpha, x, r, p, y, r32);
-  const double t = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// Per-block partial sums of a . (double)b32: dot_rows_kernel<double> of
-// blas.hip with the second operand promoted in registers.
-__global__ void __launch_bounds__(kBlock)
-    dot_f64_f32_kernel(RowSpace s, const double* __restrict__ a, const float* __restrict__ b32,
-                       double* __restrict__ partials) {
-  __shared__ double lds[16];
-  const double acc = bdx_rows::dot_rows<double, float>(s, a, b32);
-  const double t = block_sum(acc, lds);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-}
-
-// p = beta p + (double)z32 with beta = s[num] / s[den] (owned rows).
-__global__ void __launch_bounds__(kBlock)
-    p_update_f64_f32_kernel(RowSpace s, double* __restrict__ p, const float* __restrict__ z32,
-                            const double* __restrict__ scal, int num, int den) {
-  const double beta = scal[num] / scal[den];
-  bdx_rows::p_update_rows<double, float>(s, beta, p, z32);
+  for_each_owned(s, [&](int64_t i) { out[i] = static_cast<TO>(a[i]); });
 }
 
 }  // namespace
@@ -102,8 +60,8 @@ int bdx_cg_update_demote_f64(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int
                              double* partials, float* r32, hipStream_t st) {
   RowSpace s{L1, ld, o0, o1, o2};
   const int g = grid_for_rows(o0 * o1);
-  cg_update_demote_kernel<<<g, kBlock, 0, st>>>(s, x, r, p, y, scal, rn_slot, pap_slot,
-                                                partials, r32);
+  bdx_rows::cg_update_kernel<double, true><<<g, kBlock, 0, st>>>(s, x, r, p, y, scal, rn_slot,
+                                                                 pap_slot, partials, r32);
   return bdx_reduce_partials(partials, g, scal, out_slot, st);
 }
 
@@ -114,7 +72,7 @@ int bdx_dot_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, 
                     hipStream_t st) {
   RowSpace s{L1, ld, o0, o1, o2};
   const int g = grid_for_rows(o0 * o1);
-  dot_f64_f32_kernel<<<g, kBlock, 0, st>>>(s, a, b32, partials);
+  bdx_rows::dot_rows_kernel<double, float><<<g, kBlock, 0, st>>>(s, a, b32, partials);
   return bdx_reduce_partials(partials, g, out, slot, st);
 }
 
@@ -123,7 +81,8 @@ int bdx_p_update_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t
                          const float* z32, const double* scal, int num, int den,
                          hipStream_t st) {
   RowSpace s{L1, ld, o0, o1, o2};
-  p_update_f64_f32_kernel<<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(s, p, z32, scal, num, den);
+  bdx_rows::p_update_kernel<double, float><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(
+      s, p, z32, scal, num, den);
   return static_cast<int>(hipGetLastError());
 }
 

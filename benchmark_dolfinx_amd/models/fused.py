@@ -241,13 +241,7 @@ class FusedLaplacianGPU:
             else:
                 cg.z.zero_()
             k.pcg_p_update(cg.z, r, cg.dinv, cg.scal, cg.ZERO, cg.ONE)
-            k.dot(cg.z, r, cg.partials, cg.scal, cg.RR0)
-            cg._allreduce(cg.RR0)
-            k.dot(r, r, cg.partials, cg.scal, cg.RNORM)
-            cg._allreduce(cg.RNORM)
-        else:
-            k.dot(r, r, cg.partials, cg.scal, cg.RR0)
-            cg._allreduce(cg.RR0)
+        cg.rho0(cg.z if pc else r, r)
         if self.p_old is None:
             self.p_old = self.pb.new_vector()
             self.p_new = self.pb.new_vector()
@@ -283,8 +277,7 @@ class FusedLaplacianGPU:
         k, r, y, x, scal = cg.k, cg.r, cg.y, cg.x, cg.scal
         halo = self.pb.halo
         for _ in range(n):
-            cur = cg.RR0 if cg.it % 2 == 0 else cg.RR1
-            nxt = cg.RR1 if cg.it % 2 == 0 else cg.RR0
+            cur, nxt = cg.slots()
             halo.forward(r)
             bnum, bden = (cur, nxt) if cg.it > 0 else (-1, -1)
             self._launch(1, r, self.p_old, self.p_new, y, scal, bnum, bden)
@@ -314,8 +307,7 @@ class FusedLaplacianGPU:
         upd = getattr(self.lib, f"bdx_{'pcg' if pc else 'cg'}_update_iface_{pb.suf}")
         pc_args = (ptr(cg.dinv), ptr(cg.z), cg.RNORM, ptr(cg.partials_rr)) if pc else ()
         for _ in range(n):
-            cur = cg.RR0 if cg.it % 2 == 0 else cg.RR1
-            nxt = cg.RR1 if cg.it % 2 == 0 else cg.RR0
+            cur, nxt = cg.slots()
             halo.forward(u)
             bnum, bden = (cur, nxt) if cg.it > 0 else (-1, -1)
             xnum, xden = (nxt, cg.PAP) if self.x_lag else (-1, -1)
@@ -344,7 +336,7 @@ class FusedLaplacianGPU:
         """Apply the pending x += alpha_last p_last of the lagged update."""
         if not self.x_lag:
             return
-        last = cg.RR0 if (cg.it - 1) % 2 == 0 else cg.RR1
+        last = cg.slots()[1]  # the slot the last iteration read: its alpha's numerator
         _check(getattr(self.lib, f"bdx_xflush_{self.pb.suf}")(
             ptr(self.pb.latd), ptr(self._own), ptr(cg.x), ptr(self.p_old), ptr(cg.scal), last,
             cg.PAP, _stream()), "xflush")

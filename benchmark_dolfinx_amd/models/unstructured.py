@@ -130,7 +130,7 @@ class DofmapLaplacianGPU:
     """
 
     name = "dofmap"
-    RR0, RR1, PAP = 0, 1, 2  # DeviceCG's scalar slots
+    PAP = 2  # DeviceCG's scalar slot of p.Ap
 
     def __init__(self, problem, geometry: str = "otf", mesh: UnstructuredMesh | None = None,
                  runtime: str | None = None):
@@ -212,8 +212,7 @@ class DofmapLaplacianGPU:
         pb, k = self.pb, self.k
         self.apply(x, cg.y)
         k.axpy(cg.r, -1.0, cg.y, b)
-        k.dot(cg.r, cg.r, cg.partials, cg.scal, self.RR0)
-        cg._allreduce(self.RR0)
+        cg.rho0(cg.r, cg.r)
         n = pb.lat.nstore
         if getattr(self, "p_a", None) is None:
             # allocated once: the native runtime keeps pointers to them
@@ -254,7 +253,7 @@ class DofmapLaplacianGPU:
         r, y, x, scal = cg.r.view(-1), cg.y.view(-1), cg.x.view(-1), cg.scal
         for _ in range(n):
             it = cg.it
-            cur, nxt = (self.RR0, self.RR1) if it % 2 == 0 else (self.RR1, self.RR0)
+            cur, nxt = cg.slots()
             pold, pnew = (self.p_a, self.p_b) if it % 2 == 0 else (self.p_b, self.p_a)
             kw = dict(mode=1, pold=pold, pnew=pnew, x=x, scal=scal,
                       beta=(-1, -1) if it == 0 else (cur, nxt),
@@ -278,7 +277,7 @@ class DofmapLaplacianGPU:
         """Apply the lagged x += alpha p of the last iteration."""
         if not self.x_lag:
             return
-        last = self.RR0 if (cg.it - 1) % 2 == 0 else self.RR1
+        last = cg.slots()[1]  # the slot the last iteration read
         plast = self.p_b if (cg.it - 1) % 2 == 0 else self.p_a
         self.k.dofmap_xflush(cg.x.view(-1), plast, cg.scal, last, self.PAP)
         self.x_lag = False

@@ -6,17 +6,21 @@ precond=...)`), such as the p-multigrid V-cycle of solvers/pmg.py
 (`DeviceCG(pb, precond="pmg")`).
 
 Two implementations with the reference's algorithm (x0 given, r0 = b - A x0,
-p0 = r0, rtol = 0 runs exactly max_iter iterations):
+p0 = z0 = M^-1 r0, rtol = 0 runs exactly max_iter iterations).  Each holds the
+recurrence once; a preconditioner only changes how z and rho = r.z are formed:
 
 * `cg_solve`: generic, host scalars (used by the CPU platform and the CSR
-  comparison path).
-* `cg_solve_device`: GPU, every scalar stays on the device.  Per iteration:
-  apply (+ halo), dot(p, y) -> all-reduce, fused {x += a p; r -= a y;
-  r.r} -> all-reduce, p = b p + r.  alpha/beta are formed inside the kernels
-  from float64 device slots, ping-ponging the r.r slot between iterations
-  so no kernel reads a slot another kernel of the same iteration writes.
-  One halo exchange per iteration (the reference does two, quirk Q2) and no
-  host synchronisation (quirk Q3).
+  comparison path).  z = M^-1 r comes from one callable; without a
+  preconditioner z is r itself.
+* `DeviceCG` (`cg_solve_device`): GPU, every scalar stays on the device.  Per
+  iteration the common head, apply (+ halo), dot(p, y) -> all-reduce, then the
+  preconditioner's tail: {x += a p; r -= a y; r.r}, z, rho = r.z ->
+  all-reduce, p = b p + z (unpreconditioned: the fused cg_update, then
+  p_update).  alpha/beta are formed inside the kernels from float64 device
+  slots, ping-ponging the rho slot between iterations (`DeviceCG.slots`) so no
+  kernel reads a slot another kernel of the same iteration writes.  One halo
+  exchange per iteration (the reference does two, quirk Q2) and no host
+  synchronisation (quirk Q3).
 
 When the operator provides `cg_start` / `cg_iterate` (the fused structured
 kernel, models/fused.py) the device loop delegates to it.  The preconditioned
@@ -35,99 +39,55 @@ def cg_solve(op, pb, x: torch.Tensor, b: torch.Tensor, max_iter: int,
     """`dinv` (lattice-shaped 1 / diag(A), `PoissonProblem.jacobi_inverse`):
     Jacobi-preconditioned CG; `precond`: a callable `precond(r, z)` that
     writes z = M^-1 r (e.g. `PMultigrid.apply`); neither: the unpreconditioned
-    algorithm."""
+    algorithm.  Standard PCG: beta = r.z (new) / r.z (old), stop test on r.r
+    (the reference's hook for the diagonal: MatrixOperator::get_diag_inverse,
+    src/csr.hpp:81-106)."""
     if dinv is not None and precond is not None:
         raise ValueError("give dinv or precond, not both")
     if dinv is not None:
-        return _pcg_solve(op, pb, x, b, max_iter, rtol, dinv)
+        def precond(r, z):
+            torch.mul(dinv, r, out=z)
+    r = pb.new_vector()
+    y = pb.new_vector()
+    op.apply(x, y)
+    r.copy_(b - y)
+    # unpreconditioned: z is r, so r.z is the r.r of the stop test
+    z = r if precond is None else pb.new_vector()
     if precond is not None:
-        return _pcg_solve_callable(op, pb, x, b, max_iter, rtol, precond)
-    r = pb.new_vector()
-    y = pb.new_vector()
-    op.apply(x, y)
-    r.copy_(b - y)
-    p = r.clone()
-    rnorm0 = pb.inner(p, r)
-    rnorm = rnorm0
-    rtol2 = rtol * rtol
-    k = 0
-    while k < max_iter:
-        k += 1
-        op.apply(p, y)
-        alpha = rnorm / pb.inner(p, y)
-        x.add_(p, alpha=alpha)
-        r.add_(y, alpha=-alpha)
-        rnorm_new = pb.inner(r, r)
-        beta = rnorm_new / rnorm
-        rnorm = rnorm_new
-        if rnorm0 > 0 and rnorm / rnorm0 < rtol2:
-            break
-        p.mul_(beta).add_(r)
-    return k
-
-
-def _pcg_solve(op, pb, x, b, max_iter: int, rtol: float, dinv) -> int:
-    """Standard PCG with M^-1 = diag(dinv): z = dinv . r, beta = r.z (new) /
-    r.z (old), stop test on r.r (the reference's hook for it:
-    MatrixOperator::get_diag_inverse, src/csr.hpp:81-106)."""
-    r = pb.new_vector()
-    y = pb.new_vector()
-    op.apply(x, y)
-    r.copy_(b - y)
-    z = dinv * r
-    p = z.clone()
-    rz = pb.inner(r, z)
-    rtol2 = rtol * rtol
-    rnorm0 = pb.inner(r, r) if rtol2 > 0 else 0.0
-    k = 0
-    while k < max_iter:
-        k += 1
-        op.apply(p, y)
-        alpha = rz / pb.inner(p, y)
-        x.add_(p, alpha=alpha)
-        r.add_(y, alpha=-alpha)
-        torch.mul(dinv, r, out=z)
-        rz_new = pb.inner(r, z)
-        beta = rz_new / rz
-        rz = rz_new
-        if rnorm0 > 0 and pb.inner(r, r) / rnorm0 < rtol2:
-            break
-        p.mul_(beta).add_(z)
-    return k
-
-
-def _pcg_solve_callable(op, pb, x, b, max_iter: int, rtol: float, precond) -> int:
-    """PCG with z = M^-1 r computed by `precond(r, z)`; same recurrence and
-    stop test as `_pcg_solve`."""
-    r = pb.new_vector()
-    y = pb.new_vector()
-    z = pb.new_vector()
-    op.apply(x, y)
-    r.copy_(b - y)
-    precond(r, z)
-    p = z.clone()
-    rz = pb.inner(r, z)
-    rtol2 = rtol * rtol
-    rnorm0 = pb.inner(r, r) if rtol2 > 0 else 0.0
-    k = 0
-    while k < max_iter:
-        k += 1
-        op.apply(p, y)
-        alpha = rz / pb.inner(p, y)
-        x.add_(p, alpha=alpha)
-        r.add_(y, alpha=-alpha)
         precond(r, z)
+    p = z.clone()
+    rz = pb.inner(r, z)
+    rtol2 = rtol * rtol
+    if precond is None:
+        rnorm0 = rz
+    else:
+        rnorm0 = pb.inner(r, r) if rtol2 > 0 else 0.0
+    k = 0
+    while k < max_iter:
+        k += 1
+        op.apply(p, y)
+        alpha = rz / pb.inner(p, y)
+        x.add_(p, alpha=alpha)
+        r.add_(y, alpha=-alpha)
+        if precond is not None:
+            precond(r, z)
         rz_new = pb.inner(r, z)
         beta = rz_new / rz
         rz = rz_new
-        if rnorm0 > 0 and pb.inner(r, r) / rnorm0 < rtol2:
-            break
+        if rnorm0 > 0:
+            rnorm = rz if precond is None else pb.inner(r, r)
+            if rnorm / rnorm0 < rtol2:
+                break
         p.mul_(beta).add_(z)
     return k
 
 
 class DeviceCG:
     """Device-resident CG state for the GPU platform.
+
+    One prologue and one loop (`start`, `iterate`); the preconditioner picks,
+    once in `__init__`, the pair of methods that form the first direction and
+    the tail of an iteration (`_first_*`, `_tail_*`).
 
     precond="jacobi": Jacobi-preconditioned CG with the problem's matrix-free
     diagonal.  loop="generic" (default) runs op.apply + dot + pcg_update +
@@ -150,8 +110,8 @@ class DeviceCG:
 
     # float64 scalar slots
     RR0, RR1, PAP = 0, 1, 2
-    # Jacobi PCG: RR0 / RR1 carry r.z, RNORM the plain r.r; ZERO / ONE give the
-    # prologue's beta = 0 (slots 3, 4: the fused kernels' lagged alphas)
+    # preconditioned: RR0 / RR1 carry r.z, RNORM the plain r.r; ZERO / ONE give
+    # the Jacobi prologue's beta = 0 (slots 3, 4: the fused kernels' lagged alphas)
     RNORM, ZERO, ONE = 5, 6, 7
 
     def __init__(self, pb, precond: str | None = None, loop: str = "generic", pmg=None):
@@ -189,6 +149,9 @@ class DeviceCG:
             self.z = pb.new_vector()
         # the fused loop keeps its search directions in the operator
         self.p = pb.new_vector() if loop == "generic" else None
+        self._first, self._tail = self._MODES[
+            "mixed" if self.mixed else "pmg" if self.pmg is not None
+            else "jacobi" if self.dinv is not None else "plain"]
 
     @property
     def fused_pcg(self) -> bool:
@@ -203,131 +166,117 @@ class DeviceCG:
         if self.pb.comm.size > 1:
             self.pb.comm.allreduce_(self.scal[slot: slot + 1])
 
-    def start(self, op, x: torch.Tensor, b: torch.Tensor) -> None:
-        """r0 = b - A x0, p0 = r0, rho0 = p0.r0 (the prologue of src/cg.hpp:98-112)."""
-        self.op, self.x, self.it = op, x, 0
-        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
-        if self.fused_pcg:
-            if not getattr(op, "supports_fused_pcg", False):
-                name = getattr(op, "name", type(op).__name__)
-                raise ValueError(f"operator {name!r} has no fused preconditioned CG loop "
-                                 "(fused2, fused3 and fused5 do); use loop='generic'")
-            op.cg_start(self, x, b)
-            return
-        if self.mixed:
-            # the same prologue with z0 kept in FP32 (pmg.zc) and promoted into p0
-            pmg = self.pmg
-            op.apply(x, y)
-            k.axpy(r, -1.0, y, b)
-            k.demote(r, pmg.rc)
-            pmg.apply_cycle(pmg.rc, pmg.zc)
-            k.promote(pmg.zc, p)
-            k.dot_f64_f32(r, pmg.zc, self.partials, scal, self.RR0)
-            self._allreduce(self.RR0)
-            k.dot(r, r, self.partials, scal, self.RNORM)
-            self._allreduce(self.RNORM)
-            return
-        if self.pmg is not None:
-            # r0 = b - A x0, z0 = M^-1 r0, p0 = z0, rz0 = r0.z0, rr0 = r0.r0
-            z = self.z
-            op.apply(x, y)
-            k.axpy(r, -1.0, y, b)
-            self.pmg.apply(r, z)
-            p.copy_(z)
-            k.dot(r, z, self.partials, scal, self.RR0)
-            self._allreduce(self.RR0)
-            k.dot(r, r, self.partials, scal, self.RNORM)
-            self._allreduce(self.RNORM)
-            return
-        if self.dinv is not None:
-            # p0 = dinv . r0 (beta = 0 / 1), rz0 = p0.r0, rr0 = r0.r0
-            op.apply(x, y)
-            k.axpy(r, -1.0, y, b)
-            p.zero_()
-            k.pcg_p_update(p, r, self.dinv, scal, self.ZERO, self.ONE)
-            k.dot(p, r, self.partials, scal, self.RR0)
-            self._allreduce(self.RR0)
-            k.dot(r, r, self.partials, scal, self.RNORM)
-            self._allreduce(self.RNORM)
-            return
-        if hasattr(op, "cg_start"):
-            op.cg_start(self, x, b)
-            return
-        op.apply(x, y)
-        k.axpy(r, -1.0, y, b)
-        p.copy_(r)
-        k.dot(p, r, self.partials, scal, self.RR0)
+    def slots(self) -> tuple[int, int]:
+        """(cur, nxt): the rho slot iteration `it` reads and the one it writes
+        (ping-pong).  After an iteration `nxt` is the slot that one read."""
+        return (self.RR0, self.RR1) if self.it % 2 == 0 else (self.RR1, self.RR0)
+
+    def rho0(self, a: torch.Tensor, b: torch.Tensor, dot=None) -> None:
+        """End of a prologue: rho0 = a.b into RR0 and, preconditioned, the
+        plain r0.r0 into RNORM, each all-reduced."""
+        (dot or self.k.dot)(a, b, self.partials, self.scal, self.RR0)
         self._allreduce(self.RR0)
+        if self.dinv is not None or self.pmg is not None:
+            self.k.dot(self.r, self.r, self.partials, self.scal, self.RNORM)
+            self._allreduce(self.RNORM)
+
+    # Per preconditioner: `_first_*` forms p0 = M^-1 r0 and rho0; `_tail_*`
+    # is an iteration after the common head: the update with alpha =
+    # s[cur] / s[PAP], the new rho into s[nxt], p = (s[nxt] / s[cur]) p + z.
+    def _first_plain(self) -> None:
+        self.p.copy_(self.r)
+        self.rho0(self.p, self.r)
+
+    def _tail_plain(self, cur: int, nxt: int) -> None:
+        k, r, p, scal = self.k, self.r, self.p, self.scal
+        k.cg_update(self.x, r, p, self.y, scal, cur, self.PAP, nxt, self.partials)
+        self._allreduce(nxt)
+        k.p_update(p, r, scal, nxt, cur)
+
+    def _first_jacobi(self) -> None:
+        # p0 = dinv . r0 (beta = 0 / 1)
+        self.p.zero_()
+        self.k.pcg_p_update(self.p, self.r, self.dinv, self.scal, self.ZERO, self.ONE)
+        self.rho0(self.p, self.r)
+
+    def _tail_jacobi(self, cur: int, nxt: int) -> None:
+        k, r, p, scal = self.k, self.r, self.p, self.scal
+        k.pcg_update(self.x, r, p, self.y, self.dinv, scal, cur, self.PAP, nxt, self.RNORM,
+                     self.partials)
+        self._allreduce(nxt)
+        self._allreduce(self.RNORM)
+        k.pcg_p_update(p, r, self.dinv, scal, nxt, cur)
+
+    def _first_pmg(self) -> None:
+        self.pmg.apply(self.r, self.z)
+        self.p.copy_(self.z)
+        self.rho0(self.r, self.z)
+
+    def _tail_pmg(self, cur: int, nxt: int) -> None:
+        k, r, p, z, scal = self.k, self.r, self.p, self.z, self.scal
+        k.cg_update(self.x, r, p, self.y, scal, cur, self.PAP, self.RNORM, self.partials)
+        self._allreduce(self.RNORM)
+        self.pmg.apply(r, z)
+        k.dot(r, z, self.partials, scal, nxt)
+        self._allreduce(nxt)
+        k.p_update(p, z, scal, nxt, cur)
+
+    def _first_mixed(self) -> None:
+        # z0 kept in FP32 (pmg.zc) and promoted into p0
+        k, pmg = self.k, self.pmg
+        k.demote(self.r, pmg.rc)
+        pmg.apply_cycle(pmg.rc, pmg.zc)
+        k.promote(pmg.zc, self.p)
+        self.rho0(self.r, pmg.zc, k.dot_f64_f32)
+
+    def _tail_mixed(self, cur: int, nxt: int) -> None:
+        k, r, p, pmg, scal = self.k, self.r, self.p, self.pmg, self.scal
+        k.cg_update_demote(self.x, r, p, self.y, scal, cur, self.PAP, self.RNORM, self.partials,
+                           pmg.rc)
+        self._allreduce(self.RNORM)
+        pmg.apply_cycle(pmg.rc, pmg.zc)
+        k.dot_f64_f32(r, pmg.zc, self.partials, scal, nxt)
+        self._allreduce(nxt)
+        k.p_update_f64_f32(p, pmg.zc, scal, nxt, cur)
+
+    # Plain functions, called with the instance: a bound method kept on the
+    # instance would be a reference cycle, and the vectors would then live
+    # until the garbage collector runs instead of going with the last reference.
+    _MODES = {"plain": (_first_plain, _tail_plain), "jacobi": (_first_jacobi, _tail_jacobi),
+              "pmg": (_first_pmg, _tail_pmg), "mixed": (_first_mixed, _tail_mixed)}
+
+    def start(self, op, x: torch.Tensor, b: torch.Tensor) -> None:
+        """r0 = b - A x0, p0 = M^-1 r0, rho0 = p0.r0 (the prologue of
+        src/cg.hpp:98-112)."""
+        self.op, self.x, self.it = op, x, 0
+        if self.fused_pcg and not getattr(op, "supports_fused_pcg", False):
+            name = getattr(op, "name", type(op).__name__)
+            raise ValueError(f"operator {name!r} has no fused preconditioned CG loop "
+                             "(fused2, fused3 and fused5 do); use loop='generic'")
+        # the operator's own loop: on request for Jacobi, whenever it has one
+        # for the unpreconditioned solve
+        self._delegated = self.fused_pcg or (self._op_drives_loop and hasattr(op, "cg_start"))
+        if self._delegated:
+            op.cg_start(self, x, b)
+            return
+        op.apply(x, self.y)
+        self.k.axpy(self.r, -1.0, self.y, b)
+        self._first(self)
 
     def iterate(self, n: int, flush: bool = True) -> None:
         """Run n CG iterations (state persists across calls).  A fused
         operator lags its x update by one iteration; `flush=False` leaves the
         last one pending for the next call (x is then one update behind)."""
-        op, x = self.op, self.x
-        k, r, y, p, scal = self.k, self.r, self.y, self.p, self.scal
-        if self.fused_pcg:
-            op.cg_iterate(self, n, flush=flush)
+        if self._delegated:
+            self.op.cg_iterate(self, n, flush=flush)
             return
-        if self.mixed:
-            pmg = self.pmg
-            for _ in range(n):
-                cur = self.RR0 if self.it % 2 == 0 else self.RR1
-                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
-                op.apply(p, y)
-                k.dot(p, y, self.partials, scal, self.PAP)
-                self._allreduce(self.PAP)
-                k.cg_update_demote(x, r, p, y, scal, cur, self.PAP, self.RNORM, self.partials,
-                                   pmg.rc)
-                self._allreduce(self.RNORM)
-                pmg.apply_cycle(pmg.rc, pmg.zc)
-                k.dot_f64_f32(r, pmg.zc, self.partials, scal, nxt)
-                self._allreduce(nxt)
-                k.p_update_f64_f32(p, pmg.zc, scal, nxt, cur)
-                self.it += 1
-            return
-        if self.pmg is not None:
-            z = self.z
-            for _ in range(n):
-                cur = self.RR0 if self.it % 2 == 0 else self.RR1
-                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
-                op.apply(p, y)
-                k.dot(p, y, self.partials, scal, self.PAP)
-                self._allreduce(self.PAP)
-                k.cg_update(x, r, p, y, scal, cur, self.PAP, self.RNORM, self.partials)
-                self._allreduce(self.RNORM)
-                self.pmg.apply(r, z)
-                k.dot(r, z, self.partials, scal, nxt)
-                self._allreduce(nxt)
-                k.p_update(p, z, scal, nxt, cur)
-                self.it += 1
-            return
-        if self.dinv is not None:
-            dinv = self.dinv
-            for _ in range(n):
-                cur = self.RR0 if self.it % 2 == 0 else self.RR1
-                nxt = self.RR1 if self.it % 2 == 0 else self.RR0
-                op.apply(p, y)
-                k.dot(p, y, self.partials, scal, self.PAP)
-                self._allreduce(self.PAP)
-                k.pcg_update(x, r, p, y, dinv, scal, cur, self.PAP, nxt, self.RNORM,
-                             self.partials)
-                self._allreduce(nxt)
-                self._allreduce(self.RNORM)
-                k.pcg_p_update(p, r, dinv, scal, nxt, cur)
-                self.it += 1
-            return
-        if hasattr(op, "cg_iterate"):
-            op.cg_iterate(self, n, flush=flush)
-            return
+        op, k, y, p = self.op, self.k, self.y, self.p
         for _ in range(n):
-            cur = self.RR0 if self.it % 2 == 0 else self.RR1
-            nxt = self.RR1 if self.it % 2 == 0 else self.RR0
+            cur, nxt = self.slots()
             op.apply(p, y)
-            k.dot(p, y, self.partials, scal, self.PAP)
+            k.dot(p, y, self.partials, self.scal, self.PAP)
             self._allreduce(self.PAP)
-            k.cg_update(x, r, p, y, scal, cur, self.PAP, nxt, self.partials)
-            self._allreduce(nxt)
-            k.p_update(p, r, scal, nxt, cur)
+            self._tail(self, cur, nxt)
             self.it += 1
 
     def iterate_timed(self, n: int) -> list[float]:
@@ -366,10 +315,8 @@ class DeviceCG:
         return max_iter
 
     def residual_norm2(self) -> float:
-        if self.dinv is not None or self.pmg is not None:
-            return float(self.scal[self.RNORM].item())
-        slot = self.RR0 if self.it % 2 == 0 else self.RR1
-        return float(self.scal[slot].item())
+        preconditioned = self.dinv is not None or self.pmg is not None
+        return float(self.scal[self.RNORM if preconditioned else self.slots()[0]].item())
 
 
 def cg_solve_device(op, pb, x: torch.Tensor, b: torch.Tensor, max_iter: int) -> int:

@@ -205,6 +205,22 @@ def test_cg_without_dinv_unchanged():
     assert torch.equal(x, xr)
 
 
+@pytest.mark.parametrize("stop", [{"max_iter": 12}, {"max_iter": 200, "rtol": 1e-6}])
+def test_pcg_dinv_equals_callable(stop):
+    """`dinv=d` and `precond=` the callable that multiplies by d are one
+    recurrence: the same iteration count and bitwise the same iterate."""
+    pb = _problem((3, 2, 4), 2, 1, False, 0.2, "random")
+    op = MatFreeLaplacianCPU(pb)
+    b = pb.assemble_rhs()
+    d = pb.jacobi_inverse()
+    x_d, x_c = pb.new_vector(), pb.new_vector()
+    k_d = cg_solve(op, pb, x_d, b, dinv=d, **stop)
+    k_c = cg_solve(op, pb, x_c, b, precond=lambda r, z: torch.mul(d, r, out=z), **stop)
+    print(f"iterations: dinv {k_d}, callable {k_c}")
+    assert k_d == k_c and (k_d == 12 if "rtol" not in stop else 0 < k_d < 200)
+    assert torch.equal(x_d, x_c)
+
+
 # ------------------------------------------------------------------- CLI
 def _env():
     env = dict(os.environ)

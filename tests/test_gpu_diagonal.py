@@ -85,7 +85,10 @@ def test_diagonal_threaded_ranks(R):
 # ------------------------------------------------------ PCG vector kernels
 # owned box (5, 3, 70) inside storage (6, 4, 80): rows longer than one wave's
 # 64 lanes and no multiple of it; everything outside the owned box is NaN
-OWN, L1, LD, L0 = (5, 3, 70), 4, 80, 6
+BOX = OWN, L1, LD, L0 = (5, 3, 70), 4, 80, 6
+# the other shapes of the owned-row walk: rows shorter than a wave, and more
+# than 4 x 2048 rows (the grid-stride branch of the row loop)
+ROW_WALK_BOXES = {"short": ((3, 5, 19), 6, 32, 4), "rows": ((96, 96, 3), 97, 16, 97)}
 RZ, PAP, OUT, RR = 0, 2, 1, 5
 TYPES = {"f64": (np.float64, 1e-14), "f32": (np.float32, 1e-6)}
 NAN = float("nan")
@@ -95,7 +98,8 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.int64 if a.dtype.itemsize == 8 else np.int32)
 
 
-def _vec(rng, T, positive=False):
+def _vec(rng, T, positive=False, box=BOX):
+    OWN, L1, LD, L0 = box
     a = np.full((L0, L1, LD), NAN, dtype=T)
     v = rng.standard_normal(OWN)
     a[: OWN[0], : OWN[1], : OWN[2]] = (np.abs(v) + 0.5) if positive else v
@@ -106,26 +110,29 @@ def _dev(a):
     return torch.from_numpy(a.copy()).to("cuda")
 
 
-def _own(a):
+def _own(a, box=BOX):
+    OWN = box[0]
     return a[: OWN[0], : OWN[1], : OWN[2]]
 
 
-def _outside():
+def _outside(box=BOX):
+    OWN, L1, LD, L0 = box
     m = np.ones((L0, L1, LD), dtype=bool)
     m[: OWN[0], : OWN[1], : OWN[2]] = False
     return m
 
 
 @pytest.mark.parametrize("suf", ["f64", "f32"])
-def test_pcg_update_kernel(suf):
+def test_pcg_update_kernel(suf, box=BOX):
     """x += alpha p, r -= alpha y per entry within tol (|term| + |term|) of the
     float64 numpy value (tol 1e-14 / 1e-6: relative to the magnitude of the
     terms, the only bound a rounded sum can meet under cancellation); both
     reductions against math.fsum of the stored r within n eps sum|terms|."""
     T, tol = TYPES[suf]
+    OWN, L1, LD, L0 = box
     rng = np.random.default_rng(17)
-    x0, r0, p0, y0 = (_vec(rng, T) for _ in range(4))
-    dinv0 = _vec(rng, T, positive=True)
+    x0, r0, p0, y0 = (_vec(rng, T, box=box) for _ in range(4))
+    dinv0 = _vec(rng, T, True, box)
     scal0 = np.full(8, NAN)
     scal0[RZ], scal0[PAP] = 0.8125, 1.37
     lib = native.hip()
@@ -138,19 +145,19 @@ def test_pcg_update_kernel(suf):
     torch.cuda.synchronize()
     x1, r1, s1 = d_x.cpu().numpy(), d_r.cpu().numpy(), d_s.cpu().numpy()
     alpha = float(T(scal0[RZ] / scal0[PAP]))
-    xo, ro, po, yo = (_own(a).astype(np.float64) for a in (x0, r0, p0, y0))
-    assert np.isfinite(_own(x1)).all() and np.isfinite(_own(r1)).all()
-    ex = np.abs(_own(x1) - (xo + alpha * po)) / (np.abs(xo) + np.abs(alpha * po))
-    er = np.abs(_own(r1) - (ro - alpha * yo)) / (np.abs(ro) + np.abs(alpha * yo))
+    xo, ro, po, yo = (_own(a, box).astype(np.float64) for a in (x0, r0, p0, y0))
+    assert np.isfinite(_own(x1, box)).all() and np.isfinite(_own(r1, box)).all()
+    ex = np.abs(_own(x1, box) - (xo + alpha * po)) / (np.abs(xo) + np.abs(alpha * po))
+    er = np.abs(_own(r1, box) - (ro - alpha * yo)) / (np.abs(ro) + np.abs(alpha * yo))
     print(f"{suf} pcg_update: x err {ex.max():.3e}, r err {er.max():.3e}")
     assert ex.max() <= tol and er.max() <= tol
-    out = _outside()
+    out = _outside(box)
     assert np.array_equal(_bits(x1)[out], _bits(x0)[out])
     assert np.array_equal(_bits(r1)[out], _bits(r0)[out])
     for d, h in ((d_p, p0), (d_y, y0), (d_d, dinv0)):
         assert np.array_equal(_bits(d.cpu().numpy()), _bits(h))
-    rs = _own(r1).astype(np.float64).ravel()
-    dv = _own(dinv0).astype(np.float64).ravel()
+    rs = _own(r1, box).astype(np.float64).ravel()
+    dv = _own(dinv0, box).astype(np.float64).ravel()
     n, eps = rs.size, 2.0 ** -52
     for slot, terms in ((RR, rs * rs), (OUT, dv * rs * rs)):
         ref = math.fsum(terms)
@@ -162,12 +169,13 @@ def test_pcg_update_kernel(suf):
 
 
 @pytest.mark.parametrize("suf", ["f64", "f32"])
-def test_pcg_p_update_kernel(suf):
+def test_pcg_p_update_kernel(suf, box=BOX):
     """p = beta p + dinv . r per entry, same tolerance model."""
     T, tol = TYPES[suf]
+    OWN, L1, LD, L0 = box
     rng = np.random.default_rng(19)
-    p0, r0 = _vec(rng, T), _vec(rng, T)
-    dinv0 = _vec(rng, T, positive=True)
+    p0, r0 = _vec(rng, T, box=box), _vec(rng, T, box=box)
+    dinv0 = _vec(rng, T, True, box)
     scal0 = np.full(8, NAN)
     scal0[1], scal0[0] = 0.59375, 1.21
     lib = native.hip()
@@ -179,15 +187,24 @@ def test_pcg_p_update_kernel(suf):
     torch.cuda.synchronize()
     p1 = d_p.cpu().numpy()
     beta = float(T(scal0[1] / scal0[0]))
-    po, ro, do = (_own(a).astype(np.float64) for a in (p0, r0, dinv0))
-    assert np.isfinite(_own(p1)).all()
-    ep = np.abs(_own(p1) - (beta * po + do * ro)) / (np.abs(beta * po) + np.abs(do * ro))
+    po, ro, do = (_own(a, box).astype(np.float64) for a in (p0, r0, dinv0))
+    assert np.isfinite(_own(p1, box)).all()
+    ep = np.abs(_own(p1, box) - (beta * po + do * ro)) / (np.abs(beta * po) + np.abs(do * ro))
     print(f"{suf} pcg_p_update: p err {ep.max():.3e}")
     assert ep.max() <= tol
-    out = _outside()
+    out = _outside(box)
     assert np.array_equal(_bits(p1)[out], _bits(p0)[out])
     for d, h in ((d_r, r0), (d_d, dinv0), (d_s, scal0)):
         assert np.array_equal(_bits(d.cpu().numpy()), _bits(h))
+
+
+@pytest.mark.parametrize("suf", ["f64", "f32"])
+@pytest.mark.parametrize("box", list(ROW_WALK_BOXES))
+def test_pcg_kernels_row_walk_shapes(box, suf):
+    """The two kernels above, same checks, at the remaining shapes of the row walk."""
+    assert ROW_WALK_BOXES["short"][0][2] < 64 and math.prod(ROW_WALK_BOXES["rows"][0][:2]) > 4 * 2048
+    test_pcg_update_kernel(suf, ROW_WALK_BOXES[box])
+    test_pcg_p_update_kernel(suf, ROW_WALK_BOXES[box])
 
 
 # ------------------------------------------------------------ end to end

@@ -115,16 +115,20 @@ def test_transfer_kernels_reject_bad_descriptors():
 
 # owned box (5, 3, 70) inside storage (6, 4, 80): rows longer than one wave's
 # 64 lanes and no multiple of it; everything outside the owned box is NaN
-OWN, L1, LD, L0 = (5, 3, 70), 4, 80, 6
-SL = tuple(slice(0, n) for n in OWN)
+BOX = (5, 3, 70), 4, 80, 6
+# the other shapes of the owned-row walk: rows shorter than a wave, and more
+# than 4 x 2048 rows (the grid-stride branch of the row loop)
+ROW_WALK_BOXES = {"short": ((3, 5, 19), 6, 32, 4), "rows": ((96, 96, 3), 97, 16, 97)}
 
 
 @pytest.mark.parametrize("suf,dt", [("f64", torch.float64), ("f32", torch.float32)])
 @pytest.mark.parametrize("first", [True, False])
-def test_cheb_step_kernel_vs_host_twin(first, suf, dt):
+def test_cheb_step_kernel_vs_host_twin(first, suf, dt, box=BOX):
     """Against the host twin and numpy, each entry within 8 eps of the
     magnitude of its terms (tests/test_cpu_pmg.py::test_cheb_step_host_twin);
     bitwise untouched outside the owned box; `first` reads no y, d, z."""
+    OWN, L1, LD, L0 = box
+    SL = tuple(slice(0, n) for n in OWN)
     rng = np.random.default_rng(29)
 
     def vec(positive=False, owned=True):
@@ -170,6 +174,15 @@ def test_cheb_step_kernel_vs_host_twin(first, suf, dt):
     assert torch.equal(_bits(gd)[out], _bits(d0)[out]) and torch.equal(_bits(gz)[out], _bits(z0)[out])
     for t, t0 in zip(dev[:3], (dinv, r, y)):
         assert torch.equal(_bits(t.cpu()), _bits(t0))
+
+
+@pytest.mark.parametrize("suf,dt", [("f64", torch.float64), ("f32", torch.float32)])
+@pytest.mark.parametrize("first", [True, False])
+@pytest.mark.parametrize("box", list(ROW_WALK_BOXES))
+def test_cheb_step_kernel_row_walk_shapes(box, first, suf, dt):
+    """The same checks at the remaining shapes of the row walk."""
+    assert ROW_WALK_BOXES["short"][0][2] < 64 and math.prod(ROW_WALK_BOXES["rows"][0][:2]) > 4 * 2048
+    test_cheb_step_kernel_vs_host_twin(first, suf, dt, ROW_WALK_BOXES[box])
 
 
 def test_entry_points_are_declared():
