@@ -17,7 +17,8 @@ a p-multigrid V-cycle; --pmg_smooth N / --pmg_coarse N: Chebyshev degree of
 its smoothers / of its coarsest-level solve; --pmg_hlevels N: geometric
 h-levels under its degree-1 level, -1 = as many as the mesh allows;
 --pmg_float {32,64}: precision of its V-cycle, 32 under --float 64 = the
-mixed-precision solve),
+mixed-precision solve; --pmg_tail N: its trailing degree-1 levels of at most
+N nodes run in one kernel launch, one rank only),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -91,6 +92,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pmg_float", type=int, default=None, choices=[32, 64],
                     help="Float size of the p-multigrid V-cycle (--cg --precond pmg; default: "
                          "--float): 32 with --float 64 runs the FP32 cycle inside the FP64 CG")
+    ap.add_argument("--pmg_tail", type=int, default=0,
+                    help="Run the trailing degree-1 levels of the p-multigrid V-cycle that have "
+                         "at most N local nodes in one kernel launch (--cg --precond pmg, one "
+                         "rank): 0 = off, N <= 32768")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -111,6 +116,10 @@ def parse_args(argv=None):
         raise SystemExit("error: Option 'pmg_float' needs 'cg' and 'precond pmg'")
     if args.pmg_float is not None and args.pmg_float > args.float:
         raise SystemExit("error: Option 'pmg_float' cannot exceed 'float'")
+    if args.pmg_tail < 0 or args.pmg_tail > 32768:
+        raise SystemExit("error: Option 'pmg_tail' must be 0 or a node count up to 32768")
+    if args.pmg_tail != 0 and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_tail' needs 'cg' and 'precond pmg'")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
@@ -145,6 +154,9 @@ def main(argv=None) -> int:
     if args.pcg_loop == "fused" and platform != "gpu":
         raise SystemExit("error: Option 'pcg_loop fused' needs the gpu platform")
     comm = init_distributed(platform)
+    if args.pmg_tail != 0 and comm.size > 1:
+        finalize()
+        raise SystemExit("error: Option 'pmg_tail' needs a single rank")
     log = init_logging(unknown, comm.rank)
     size = comm.size
     ndofs = args.ndofs if args.ndofs is not None else 1000
@@ -218,6 +230,8 @@ def run_benchmark(comm, nx, args, platform):
                 "h_levels": args.pmg_hlevels}
     if args.pmg_float is not None:
         pmg_opts["cycle_dtype"] = torch.float64 if args.pmg_float == 64 else torch.float32
+    if args.pmg_tail != 0:
+        pmg_opts["tail_nodes"] = args.pmg_tail
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,

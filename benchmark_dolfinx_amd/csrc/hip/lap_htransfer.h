@@ -54,14 +54,11 @@ __device__ __forceinline__ bool htransfer_piece(const BdxLattice& l, int64_t npi
   return k < l.L[2];
 }
 
-// vf (+)= P vc: one thread per fine node.
+// P vc at fine node (i, j, k): the per-node body of the prolongation (also the
+// V-cycle tail's, pmg_tail.h).
 template <typename T>
-__global__ void __launch_bounds__(kHTransferThreads)
-    lap_hprolong_kernel(BdxLattice lc, BdxLattice lf, HTransferTables<T> tab, int64_t npiece,
-                        const T* __restrict__ vc, T* __restrict__ vf, int add) {
-  int64_t i, j, k;
-  if (!htransfer_piece(lf, npiece, i, j, k)) return;
-  if (add && !lf.is_owned(i, j, k)) return;
+__device__ __forceinline__ T hprolong_node(const BdxLattice& lc, const HTransferTables<T>& tab,
+                                           const T* vc, int64_t i, int64_t j, int64_t k) {
   const int64_t ci = tab.cidx[0][i], cj = tab.cidx[1][j], ck = tab.cidx[2][k];
   const T wi = tab.cw[0][i], wj = tab.cw[1][j], wk = tab.cw[2][k];
   const int na = wi != 0 ? 2 : 1, nb = wj != 0 ? 2 : 1;
@@ -77,7 +74,18 @@ __global__ void __launch_bounds__(kHTransferThreads)
     }
     gx[a] = nb == 2 ? gy[0] + wj * (gy[1] - gy[0]) : gy[0];
   }
-  const T out = na == 2 ? gx[0] + wi * (gx[1] - gx[0]) : gx[0];
+  return na == 2 ? gx[0] + wi * (gx[1] - gx[0]) : gx[0];
+}
+
+// vf (+)= P vc: one thread per fine node.
+template <typename T>
+__global__ void __launch_bounds__(kHTransferThreads)
+    lap_hprolong_kernel(BdxLattice lc, BdxLattice lf, HTransferTables<T> tab, int64_t npiece,
+                        const T* __restrict__ vc, T* __restrict__ vf, int add) {
+  int64_t i, j, k;
+  if (!htransfer_piece(lf, npiece, i, j, k)) return;
+  if (add && !lf.is_owned(i, j, k)) return;
+  const T out = hprolong_node<T>(lc, tab, vc, i, j, k);
   const int64_t to = lf.idx(i, j, k);
   if (!BDX_OOB(to, lf.size(), "hprolong store")) vf[to] = add ? vf[to] + out : out;
 }
@@ -98,13 +106,12 @@ __device__ __forceinline__ T hrestrict_weight(const T* cw, int64_t f, int64_t mi
   return f < mid ? cw[f] : (f == mid ? T(1) : T(1) - cw[f]);
 }
 
-// vc = P^T (vf - y): one thread per coarse node, a fixed-order gather.
+// P^T (vf - y) at coarse node (i, j, k), a fixed-order gather: the per-node
+// body of the restriction (also the V-cycle tail's, pmg_tail.h).
 template <typename T>
-__global__ void __launch_bounds__(kHTransferThreads)
-    lap_hrestrict_kernel(BdxLattice lc, BdxLattice lf, HTransferTables<T> tab, int64_t npiece,
-                         const T* __restrict__ vf, const T* __restrict__ y, T* __restrict__ vc) {
-  int64_t i, j, k;
-  if (!htransfer_piece(lc, npiece, i, j, k)) return;
+__device__ __forceinline__ T hrestrict_node(const BdxLattice& lc, const BdxLattice& lf,
+                                            const HTransferTables<T>& tab, const T* vf, const T* y,
+                                            int64_t i, int64_t j, int64_t k) {
   int64_t lo[3], mid[3], hi[3];
   hrestrict_range(tab.fpos[0], i, lc.L[0], lf.L[0] - lf.gh[0], lo[0], mid[0], hi[0]);
   hrestrict_range(tab.fpos[1], j, lc.L[1], lf.L[1] - lf.gh[1], lo[1], mid[1], hi[1]);
@@ -124,6 +131,17 @@ __global__ void __launch_bounds__(kHTransferThreads)
     }
     sx += hrestrict_weight(tab.cw[0], fi, mid[0]) * sy;
   }
+  return sx;
+}
+
+// vc = P^T (vf - y): one thread per coarse node.
+template <typename T>
+__global__ void __launch_bounds__(kHTransferThreads)
+    lap_hrestrict_kernel(BdxLattice lc, BdxLattice lf, HTransferTables<T> tab, int64_t npiece,
+                         const T* __restrict__ vf, const T* __restrict__ y, T* __restrict__ vc) {
+  int64_t i, j, k;
+  if (!htransfer_piece(lc, npiece, i, j, k)) return;
+  const T sx = hrestrict_node<T>(lc, lf, tab, vf, y, i, j, k);
   const int64_t to = lc.idx(i, j, k);
   if (!BDX_OOB(to, lc.size(), "hrestrict store")) vc[to] = sx;
 }
@@ -143,7 +161,7 @@ inline bool htransfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
 }
 
 template <typename T>
-inline HTransferTables<T> htransfer_tables(const BdxLattice& lc, const BdxLattice& lf,
+__host__ __device__ inline HTransferTables<T> htransfer_tables(const BdxLattice& lc, const BdxLattice& lf,
                                            const int* cidx, const T* cw, const int* fpos) {
   HTransferTables<T> t;
   int64_t of = 0, oc = 0;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../include/bdx_lattice.h"
+#include "../include/bdx_pmg_tail.h"
 #include "../include/bdx_watchdog.h"
 
 namespace {
@@ -1080,6 +1081,111 @@ void convert_rows_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o
     }
 }
 
+// ------------------------------------------------------ V-cycle tail
+// Host twin of csrc/hip/pmg_tail.h: the levels of the table (bdx_pmg_tail.h)
+// walked down then up with the schedule of `PMultigrid._vcycle`, the operator
+// of every level its 27-point stencil S[27][nstore], plane (di + 1) 9 +
+// (dj + 1) 3 + (dk + 1), the neighbours inside the lattice in ascending plane
+// order; the Chebyshev step and the transfers are the host twins above.
+template <typename T>
+void stencil_host(const BdxLattice& lat, const T* S, const T* z, T* y) {
+  const int64_t ns = lat.size();
+  for (int64_t i = 0; i < lat.L[0]; ++i)
+    for (int64_t j = 0; j < lat.L[1]; ++j)
+      for (int64_t k = 0; k < lat.L[2]; ++k) {
+        const int64_t at = lat.idx(i, j, k);
+        T s = 0;
+        for (int64_t di = -1; di <= 1; ++di)
+          for (int64_t dj = -1; dj <= 1; ++dj)
+            for (int64_t dk = -1; dk <= 1; ++dk) {
+              if (i + di < 0 || i + di >= lat.L[0] || j + dj < 0 || j + dj >= lat.L[1] ||
+                  k + dk < 0 || k + dk >= lat.L[2])
+                continue;
+              const int64_t p = (di + 1) * 9 + (dj + 1) * 3 + (dk + 1);
+              s += S[p * ns + at] * z[lat.idx(i + di, j + dj, k + dk)];
+            }
+        y[at] = s;
+      }
+}
+
+template <typename T>
+struct TailLevelHost {
+  const int64_t* latd;
+  BdxLattice lat;
+  const T *S, *dinv;
+  const unsigned char* bc;
+  T *r, *z, *d, *y;
+  const int* cidx;
+  const T* cw;
+  const int* fpos;
+  int64_t ncoef;
+  const double* coef;
+};
+
+template <typename P>
+P tail_ptr(int64_t w) {
+  return reinterpret_cast<P>(static_cast<uintptr_t>(w));
+}
+
+template <typename T>
+TailLevelHost<T> tail_level_host(const int64_t* tab, int l, const T* r0, T* z0) {
+  const int64_t* w = tab + static_cast<int64_t>(l) * kTailWords;
+  TailLevelHost<T> v;
+  v.latd = w;
+  v.lat = BdxLattice::from(w);
+  v.S = tail_ptr<const T*>(w[kTailS]);
+  v.dinv = tail_ptr<const T*>(w[kTailDinv]);
+  v.bc = tail_ptr<const unsigned char*>(w[kTailBc]);
+  v.r = l == 0 ? const_cast<T*>(r0) : tail_ptr<T*>(w[kTailR]);
+  v.z = l == 0 ? z0 : tail_ptr<T*>(w[kTailZ]);
+  v.d = tail_ptr<T*>(w[kTailD]);
+  v.y = tail_ptr<T*>(w[kTailY]);
+  v.cidx = tail_ptr<const int*>(w[kTailCidx]);
+  v.cw = tail_ptr<const T*>(w[kTailCw]);
+  v.fpos = tail_ptr<const int*>(w[kTailFpos]);
+  v.ncoef = w[kTailNcoef];
+  v.coef = reinterpret_cast<const double*>(tab + w[kTailCoef]);
+  return v;
+}
+
+template <typename T>
+void tail_smooth_host(const TailLevelHost<T>& v, bool zero_guess) {
+  const BdxLattice& l = v.lat;
+  for (int64_t s = 0; s < v.ncoef; ++s) {
+    const T a = static_cast<T>(v.coef[2 * s]), b = static_cast<T>(v.coef[2 * s + 1]);
+    const bool first = s == 0 && zero_guess;
+    if (!first) stencil_host<T>(l, v.S, v.z, v.y);
+    cheb_step_host<T>(l.L[1], l.ld, l.L[0], l.L[1], l.L[2], first, a, b, v.dinv, v.r, v.y, v.d,
+                      v.z);
+  }
+}
+
+template <typename T>
+int pmg_tail_host(const int64_t* tab, int nlev, int64_t nwords, const T* r, T* z) {
+  if (!r || !z || !tail_table_ok(tab, nlev, nwords, htransfer_pair_ok)) return 1;
+  for (int l = 0; l < nlev; ++l) {
+    const TailLevelHost<T> v = tail_level_host<T>(tab, l, r, z);
+    tail_smooth_host(v, true);
+    if (l == nlev - 1) break;
+    const TailLevelHost<T> c = tail_level_host<T>(tab, l + 1, r, z);
+    stencil_host<T>(v.lat, v.S, v.z, v.y);
+    if (hrestrict_host<T>(c.latd, v.latd, v.cidx, v.cw, v.fpos, v.r, v.y, c.r)) return 1;
+    for (int64_t i = 0; i < c.lat.L[0]; ++i)
+      for (int64_t j = 0; j < c.lat.L[1]; ++j)
+        for (int64_t k = 0; k < c.lat.L[2]; ++k) {
+          const int64_t at = c.lat.idx(i, j, k);
+          if (c.bc[at]) c.r[at] = 0;
+        }
+  }
+  for (int l = nlev - 2; l >= 0; --l) {
+    const TailLevelHost<T> v = tail_level_host<T>(tab, l, r, z);
+    const TailLevelHost<T> c = tail_level_host<T>(tab, l + 1, r, z);
+    if (hprolong_host<T>(c.latd, v.latd, v.cidx, v.cw, v.fpos, c.z, v.z, 1)) return 1;
+    tail_smooth_host(v, false);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1224,6 +1330,18 @@ int bdx_host_version() { return 1; }
                                const T* y, T* d, T* z) {                      \
     cheb_step_host<T>(L1, ld, o0, o1, o2, first, static_cast<T>(a),           \
                       static_cast<T>(b), dinv, r, y, d, z);                   \
+  }                                                                           \
+  /* the V-cycle from the first level of the table (bdx_pmg_tail.h) down and */ \
+  /* back up, z = M r: the host twin of bdx_pmg_tail, nonzero for a bad table */ \
+  int bdx_cpu_pmg_tail_##SUF(const int64_t* tab, int nlev, int64_t nwords,    \
+                             const T* r, T* z) {                              \
+    return pmg_tail_host<T>(tab, nlev, nwords, r, z);                         \
+  }                                                                           \
+  /* y = A z with the 27-point stencil S of the degree-1 lattice latd (the  */ \
+  /* tail's operator, alone)                                                */ \
+  void bdx_cpu_stencil27_##SUF(const int64_t* latd, const T* S, const T* z,   \
+                               T* y) {                                        \
+    stencil_host<T>(BdxLattice::from(latd), S, z, y);                         \
   }                                                                           \
   int64_t bdx_cpu_csr_##SUF(const int64_t* latd, int nq, const T* B,          \
                             const T* Dd, const T* wts, const T* qpts,         \

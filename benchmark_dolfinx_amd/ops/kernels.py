@@ -82,6 +82,82 @@ class HTransferTables:
             raise ValueError("h-transfer tables do not belong to this lattice pair")
 
 
+def stencil27(A, lat) -> np.ndarray:
+    """The assembled degree-1 operator `A` (a `CSROperator` on the lattice
+    `lat`) as a 27-point stencil S[27][nstore] in the storage index: plane
+    (di + 1) 9 + (dj + 1) 3 + (dk + 1) holds row n's entry in the column of
+    its lattice neighbour (di, dj, dk); rows of the storage padding are zero.
+    Raises if an entry's column is not a lattice neighbour of its row."""
+    if lat.degree != 1:
+        raise ValueError("stencil27 needs a degree-1 lattice")
+    row_ptr, cols, vals = A._host
+    L1, L2, ld = int(lat.L[1]), int(lat.L[2]), int(lat.ld)
+    rows = np.repeat(np.arange(lat.nstore, dtype=np.int64), np.diff(row_ptr))
+    cols = cols.astype(np.int64)
+    rk, ck = rows % ld, cols % ld
+    ri, ci = rows // ld // L1, cols // ld // L1
+    rj, cj = rows // ld % L1, cols // ld % L1
+    di, dj, dk = ci - ri, cj - rj, ck - rk
+    if np.any(rk >= L2) or np.any(ck >= L2) or np.any(np.abs(di) > 1) or np.any(np.abs(dj) > 1) \
+            or np.any(np.abs(dk) > 1):
+        raise ValueError("stencil27: a matrix entry is not a lattice neighbour of its row")
+    S = np.zeros((27, lat.nstore), dtype=vals.dtype)
+    S[(di + 1) * 9 + (dj + 1) * 3 + (dk + 1), rows] = vals
+    return S
+
+
+class PmgTail:
+    """The device data of the V-cycle tail (csrc/hip/pmg_tail.h): per level of
+    `levels` (consecutive degree-1 levels of a `PMultigrid`, the last one its
+    coarsest) the 27-point stencil of the assembled operator, and one level
+    table (csrc/include/bdx_pmg_tail.h) with every level's descriptor, the
+    pointers of its stencil, `dinv`, `bc`, work vectors and transfer tables,
+    and its Chebyshev coefficients, kept on the host (`host`, read by the
+    launch checks) and on the device (`dev`, read by the kernel).  Everything
+    is uploaded here, once; the tensors the table points to are kept alive."""
+
+    WORDS = 40          # kTailWords
+    MAX_NODES = 32768   # kTailMaxNodes
+
+    def __init__(self, levels, dtype, device):
+        from ..models.poisson import CSROperator  # models.poisson imports this module
+        self.nlev = len(levels)
+        self.dtype = dtype
+        self.shape = tuple(levels[0].pb.lat.shape)
+        W = self.WORDS
+        tab = np.zeros(self.nlev * W + 2 * sum(len(lv.coef) for lv in levels), dtype=np.int64)
+        coef = tab.view(np.float64)
+        self.S, self._keep = [], []
+        off = self.nlev * W
+        for l, lv in enumerate(levels):
+            S = torch.from_numpy(stencil27(CSROperator(lv.pb), lv.pb.lat)).to(device)
+            self.S.append(S)
+            w = tab[l * W: (l + 1) * W]
+            w[:21] = lv.latd
+            vecs = [S, lv.dinv, lv.bc, lv.r, lv.z, lv.d, lv.y]
+            if l < self.nlev - 1:
+                lv.H.check(levels[l + 1].latd, lv.latd)
+                vecs += [lv.H.cidx, lv.H.cw, lv.H.fpos]
+            for v in vecs[:2] + vecs[3:7] + vecs[8:9]:
+                if v is not None and v.dtype != dtype:
+                    raise TypeError(f"tail level {l}: expected {dtype} data, got {v.dtype}")
+            w[21: 21 + len(vecs)] = [ptr(v) for v in vecs]
+            w[31], w[32] = len(lv.coef), off
+            for a, b in lv.coef:
+                coef[off], coef[off + 1] = a, b
+                off += 2
+            self._keep.append(vecs)
+        self.nwords = int(tab.size)
+        self.host = tab
+        self.dev = torch.from_numpy(tab).to(device)
+
+    def check(self, r, z) -> None:
+        for v in (r, z):
+            if v.dtype != self.dtype or tuple(v.shape) != self.shape:
+                raise TypeError(f"expected a {self.dtype} lattice vector of shape {self.shape}, "
+                                f"got {v.dtype} {tuple(v.shape)}")
+
+
 class HipKernels:
     """Bound kernel launchers for one problem (lattice + tables + dtype)."""
 
@@ -258,6 +334,13 @@ class HipKernels:
                                         ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc), _stream()),
                "hrestrict")
 
+    def pmg_tail(self, tail: PmgTail, r, z):
+        """z = the V-cycle of the tail's levels applied to r, in one launch of
+        one workgroup (pmg_tail.h); r, z: vectors of its first level."""
+        tail.check(r, z)
+        _check(self._f("bdx_pmg_tail")(ptr(tail.host), ptr(tail.dev), tail.nlev, tail.nwords,
+                                       ptr(r), ptr(z), _stream()), "pmg_tail")
+
     # ------------------------------------- FP64 CG around an FP32 cycle
     def _rows(self, v64=(), v32=()):
         """The row-walk arguments, after checking that the float64 and
@@ -345,6 +428,15 @@ class HostKernels:
         if self._f("bdx_cpu_hrestrict")(ptr(latd_c), ptr(self.latd), ptr(tab.cidx), ptr(tab.cw),
                                         ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc)):
             raise ValueError("hrestrict: not a pair of degree-1 lattices of one partition")
+
+    def pmg_tail(self, tail: PmgTail, r, z):
+        tail.check(r, z)
+        if self._f("bdx_cpu_pmg_tail")(ptr(tail.host), tail.nlev, tail.nwords, ptr(r), ptr(z)):
+            raise ValueError("pmg_tail: not a table of small degree-1 levels of one rank")
+
+    def stencil27(self, S, z, y):
+        """y = A z with the 27-point stencil S of this (degree-1) lattice."""
+        self._f("bdx_cpu_stencil27")(ptr(self.latd), ptr(S), ptr(z), ptr(y))
 
     def _rows(self, a, da, out, do):
         for v, dt in ((a, da), (out, do)):

@@ -86,6 +86,8 @@ def host():
                 _declare(lib, f"bdx_cpu_hrestrict_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp], i32)
                 _declare(lib, f"bdx_cpu_cheb_step_{suf}",
                          [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
+                _declare(lib, f"bdx_cpu_pmg_tail_{suf}", [vp, i32, i64, vp, vp], i32)
+                _declare(lib, f"bdx_cpu_stencil27_{suf}", [vp, vp, vp, vp])
             # the precision boundary of the mixed multigrid solve
             _declare(lib, "bdx_cpu_demote_f64_f32", [i64, i64, i64, i64, i64, vp, vp])
             _declare(lib, "bdx_cpu_promote_f32_f64", [i64, i64, i64, i64, i64, vp, vp])

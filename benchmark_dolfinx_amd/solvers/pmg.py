@@ -43,6 +43,18 @@ keeps its FP64 contract by demoting r into `rc`, running `apply_cycle(rc, zc)`
 and promoting `zc` (csrc/hip/mixed.hip, host twins in csrc/host/bdx_host.cpp);
 a caller that fuses the boundary into its own kernels (`DeviceCG`) calls
 `apply_cycle` directly.  The cycle is linear in r and is applied unscaled.
+
+Tail (`tail_nodes=N > 0`, off by default): the longest suffix of the level
+list whose levels all have degree 1 and at most N local nodes runs in one
+call, `pmg_tail` (csrc/hip/pmg_tail.h: one launch of one workgroup, the phases
+separated by workgroup barriers; host twin in csrc/host/bdx_host.cpp), where
+the cycle reaches its first level.  The schedule, the coefficients, `dinv`,
+`bc` and the transfer tables are the levels' own; setup is unchanged, lambda_max
+included.  Inside the tail a level's operator is its assembled 27-point
+stencil (`ops.kernels.stencil27` of `CSROperator`), which equals the
+matrix-free operator to rounding, not bitwise: the tailed preconditioner is a
+rounding-level perturbation of the untailed one.  One rank only: the tail
+levels of a partitioned mesh would need halo exchanges inside the kernel.
 """
 
 from __future__ import annotations
@@ -115,17 +127,31 @@ class PMultigrid:
     cycle_dtype: None or the problem's dtype = the hierarchy in the problem's
     precision, level 0 being `pb` itself; torch.float32 on a float64 problem =
     the mixed mode of the module docstring (`mixed` is then True, `rc` / `zc`
-    are the FP32 level-0 work vectors and `info()` carries `cycle_float`)."""
+    are the FP32 level-0 work vectors and `info()` carries `cycle_float`).
+
+    tail_nodes: 0 = off; N > 0 = the levels of the tail (module docstring) run
+    in one `pmg_tail` call; `tail_start` is then the index of the tail's first
+    level (None: no level qualifies, the cycle is the untailed one),
+    `tail_levels` their number and `tail` the `ops.kernels.PmgTail`."""
+
+    TAIL_MAX_NODES = 32768
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
-                 h_levels: int = 0, cycle_dtype: torch.dtype | None = None):
+                 h_levels: int = 0, cycle_dtype: torch.dtype | None = None, tail_nodes: int = 0):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
             raise ValueError("smoother ranges must exceed 1")
         if isinstance(h_levels, bool) or not isinstance(h_levels, (int, np.integer)) or h_levels < -1:
             raise ValueError("h_levels must be -1 (all), 0 (none) or a positive count")
+        if isinstance(tail_nodes, bool) or not isinstance(tail_nodes, (int, np.integer)) \
+                or not 0 <= tail_nodes <= self.TAIL_MAX_NODES:
+            raise ValueError(f"tail_nodes must be 0 (off) or a node count up to "
+                             f"{self.TAIL_MAX_NODES}")
+        if tail_nodes > 0 and pb.comm.size > 1:
+            raise ValueError("tail_nodes needs a single rank: the tail levels of a partitioned "
+                             "mesh would need halo exchanges inside the kernel")
         if cycle_dtype is None:
             cycle_dtype = pb.dtype
         if cycle_dtype not in (torch.float32, torch.float64) or \
@@ -180,6 +206,18 @@ class PMultigrid:
         self.rc = self.zc = None
         if self.mixed:
             self.rc, self.zc = self.levels[0].pb.new_vector(), self.levels[0].pb.new_vector()
+        # the tail: the trailing degree-1 levels of at most tail_nodes local nodes
+        self.tail_nodes = int(tail_nodes)
+        self.tail_start, self.tail_levels, self.tail = None, 0, None
+        if self.tail_nodes > 0:
+            start = len(self.levels)
+            while start > 0 and self.levels[start - 1].pb.degree == 1 and \
+                    int(np.prod(self.levels[start - 1].pb.lat.L)) <= self.tail_nodes:
+                start -= 1
+            if start < len(self.levels):
+                from ..ops.kernels import PmgTail
+                self.tail_start, self.tail_levels = start, len(self.levels) - start
+                self.tail = PmgTail(self.levels[start:], cycle_dtype, pb.device)
 
     # ---------------------------------------------------------------- setup
     @staticmethod
@@ -249,6 +287,9 @@ class PMultigrid:
 
     def _vcycle(self, l: int, r: torch.Tensor, z: torch.Tensor) -> None:
         lv = self.levels[l]
+        if l == self.tail_start:
+            lv.k.pmg_tail(self.tail, r, z)      # this level and everything below it
+            return
         self._smooth(lv, r, z, True)
         if l == len(self.levels) - 1:
             return
@@ -292,6 +333,9 @@ class PMultigrid:
             out["h_cells"] = [list(c) for c in self.h_cells]
         if self.mixed:
             out["cycle_float"] = 32
+        if self.tail_nodes != 0:
+            out["tail_nodes"] = self.tail_nodes
+            out["tail_levels"] = self.tail_levels
         return out
 
     def close(self) -> None:

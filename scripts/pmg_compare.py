@@ -7,6 +7,8 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
   python scripts/pmg_compare.py --degree 3 --hlevels -1      (adds the hpmg column, profiles/hpmg.md)
   python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --tol2 1e-12 --no-yardsticks
                                                              (FP32 cycles, profiles/pmg_mixed.md)
+  python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --tail 512,4096,32768 --no-yardsticks
+                                                             (one-launch tail, profiles/pmg_tail.md)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -21,6 +23,10 @@ its own auto-selected operator:
   hpmg32     inside the FP64 loop, and the same for hpmg; interleaved like hpmg.  --tol2 T also
              counts and times every pmg variant's solve to the second tolerance T, and the five
              kernels of the precision boundary (csrc/hip/mixed.hip) are timed alone
+  hpmg_tN    (--tail N[,N...], with --hlevels) hpmg with PMultigrid(pb, tail_nodes=N): the
+  hpmg32_tN  trailing small levels in one launch (csrc/hip/pmg_tail.h), and the same for hpmg32;
+             interleaved like hpmg.  The "tail" block also times the tail's one call against
+             the untailed `_vcycle` of the same levels, with device events
 
 Per-iteration time: device events between the steps of `iterate_timed(n)`, per
 window the mean of the first n - 1 steps, per variant the median over the
@@ -66,6 +72,8 @@ def main(argv=None) -> int:
                     help="32: add pmg32 (and, with --hlevels, hpmg32), the FP32 V-cycle in FP64 CG")
     ap.add_argument("--tol2", type=float, default=0.0,
                     help="a second, tighter tolerance for the pmg variants' solves (0: none)")
+    ap.add_argument("--tail", default="",
+                    help="comma-separated tail_nodes values: add hpmg_tN (and hpmg32_tN) per value")
     ap.add_argument("--no-yardsticks", action="store_true",
                     help="leave out cg_fused and pcg_fused")
     a = ap.parse_args(argv)
@@ -82,6 +90,9 @@ def main(argv=None) -> int:
     if not torch.cuda.is_available():
         raise SystemExit("pmg_compare needs a GPU (no timing is taken without one)")
     torch.cuda.set_device(0)
+    tails = [int(t) for t in a.tail.split(",") if t]
+    if tails and not a.hlevels:
+        raise SystemExit("--tail needs --hlevels (the tail without h-levels is not measured)")
     nx = compute_mesh_size(a.ndofs, a.degree)
     pb = PoissonProblem(Comm(), nx, a.degree, 1, False, torch.float64, "gpu", a.perturb, a.kappa)
     b = pb.assemble_rhs()
@@ -99,6 +110,11 @@ def main(argv=None) -> int:
         elif variant == "hpmg32":
             cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels,
                                                     cycle_dtype=torch.float32))
+        elif "_t" in variant:
+            base, _, n = variant.partition("_t")
+            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(
+                pb, h_levels=a.hlevels, tail_nodes=int(n),
+                cycle_dtype=torch.float32 if base == "hpmg32" else None))
         else:
             cg = DeviceCG(pb, "pmg")
         x = pb.new_vector()
@@ -109,6 +125,8 @@ def main(argv=None) -> int:
         ("hpmg",) if a.hlevels else ())
     if a.cycle_float == 32:
         variants += ("pmg32",) + (("hpmg32",) if a.hlevels else ())
+    for n in tails:
+        variants += (f"hpmg_t{n}",) + ((f"hpmg32_t{n}",) if a.cycle_float == 32 else ())
     solves = tuple(v for v in variants if "pmg" in v)
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
@@ -268,6 +286,30 @@ def main(argv=None) -> int:
     if a.tol2 > 0:
         rec["tol2"] = {"tol": a.tol2, "iters": iters2, "true_residual": true_res2,
                        "wall_s": {v: spread(s) for v, s in wall2.items()}}
+    if tails:
+        # per tailed variant: the whole cycle, and the tail's one call against the
+        # untailed hierarchy's `_vcycle` from the same level (the launches it replaces)
+        rec["tail"] = {}
+        for v in variants:
+            if "_t" not in v:
+                continue
+            tp = state[v][1].pmg
+            up = state[v.partition("_t")[0]][1].pmg
+            blk = {"info": tp.info(), "wall_s": spread(wall[v]) if v in wall else None,
+                   "true_residual": true_res.get(v),
+                   "level_nodes": [int(lv.pb.lat.L[0] * lv.pb.lat.L[1] * lv.pb.lat.L[2])
+                                   for lv in tp.levels]}
+            if tp.mixed:
+                blk["cycle_ms"] = timed(lambda: tp.apply_cycle(tp.rc, tp.zc))
+            else:
+                blk["cycle_ms"] = timed(lambda: tp.apply(r, z))
+            if tp.tail is not None and tp.tail_start > 0:
+                s0 = tp.tail_start
+                tl, ul = tp.levels[s0], up.levels[s0]
+                blk["tail_call_ms"] = timed(lambda: tl.k.pmg_tail(tp.tail, tl.r, tl.z))
+                blk["untailed_levels_ms"] = timed(lambda: up._vcycle(s0, ul.r, ul.z))
+            rec["tail"][v] = blk
+            tp.close()
     if a.cycle_float == 32:
         # the mixed variants, and the kernels of the precision boundary alone:
         # bytes per owned dof a kernel must move (f64 8, f32 4)
