@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "bdx_debug.h"  // BDX_DASSERT, BDX_OOB: the BDX_DEBUG=1 index checks
 #include "bdx_lattice.h"
 
 #define BDX_CHECK(expr)                                                     \
@@ -61,32 +62,6 @@ __device__ __forceinline__ double dpp_row_ror8(double v) {
 // alpha_prev only, or fold two terms; the saved alpha's slot of the CG scalars.
 enum { kXSingle = 0, kXSave = 1, kXPair = 2 };
 constexpr int kScalXSave = 3;  // and kScalXSave + 1 (alternate iterations)
-
-// Debug builds (BDX_DEBUG=1: `python -m benchmark_dolfinx_amd.ops.build
-// --variant debug=-DBDX_DEBUG=1`, loaded with BDX_HIP_LIB) turn on
-// device-side checks of the operator kernels' LDS and global index paths; a
-// failing check prints the expression and aborts the process (HIP device
-// assert) instead of reading or writing out of bounds.  Release builds compile
-// them out.
-#ifndef BDX_DEBUG
-#define BDX_DEBUG 0
-#endif
-#if BDX_DEBUG
-// report (do not trap: a trapped wave would take the queue down with it)
-#define BDX_DASSERT(c) \
-  ((c) ? (void)0 : (void)printf("[bdx ASSERT] %s:%d %s\n", __FILE__, __LINE__, #c))
-// out-of-range global offset: print the first few offenders, skip the access
-#define BDX_OOB(off, n, tag)                                                        \
-  (((off) < 0 || (off) >= (n))                                                      \
-       ? (printf("[bdx OOB] %s off=%lld n=%lld block=%d thread=%d\n", tag,          \
-                 static_cast<long long>(off), static_cast<long long>(n),            \
-                 static_cast<int>(blockIdx.x), static_cast<int>(threadIdx.x)),      \
-          true)                                                                     \
-       : false)
-#else
-#define BDX_DASSERT(c) ((void)0)
-#define BDX_OOB(off, n, tag) false
-#endif
 
 // Streamed vectors (read or written once per CG iteration; every vector is
 // far larger than the 256 MiB Infinity Cache) use the default cache policy:

@@ -15,6 +15,8 @@
 //     mixed.hip).
 #include "blas_rows.h"
 
+#include "bdx_mg_bodies.h"  // cheb_entry (after the HIP runtime's BDX_HD)
+
 namespace {
 
 using bdx_rows::cg_update_kernel;
@@ -77,22 +79,14 @@ __global__ void __launch_bounds__(kBlock)
 // One step of the Chebyshev-Jacobi smoother (solvers/pmg.py) over the owned
 // rows, y = A z computed by the caller:  d = a d + b dinv (r - y);  z += d.
 // FIRST (the step from a zero guess):  d = b dinv r;  z = d, which reads
-// neither y nor the old d and z.  One pass of five reads and two writes.
+// neither y nor the old d and z.  One pass of five reads and two writes; the
+// entry update is cheb_entry (bdx_mg_bodies.h), shared with the V-cycle tail
+// and the host twin.
 template <typename T, bool FIRST>
 __global__ void __launch_bounds__(kBlock)
     cheb_step_kernel(RowSpace s, T a, T b, const T* __restrict__ dinv, const T* __restrict__ r,
                      const T* __restrict__ y, T* __restrict__ d, T* __restrict__ z) {
-  for_each_owned(s, [&](int64_t i) {
-    if constexpr (FIRST) {
-      const T dn = b * dinv[i] * r[i];
-      d[i] = dn;
-      z[i] = dn;
-    } else {
-      const T dn = a * d[i] + b * dinv[i] * (r[i] - y[i]);
-      d[i] = dn;
-      z[i] = z[i] + dn;
-    }
-  });
+  for_each_owned(s, [&](int64_t i) { cheb_entry<T>(FIRST, a, b, dinv, r, y, d, z, i); });
 }
 
 // out = alpha x + y over owned rows (reference axpy, src/vector.hpp:228-240).

@@ -27,16 +27,14 @@
 //     ascending order, x outermost, with the weights cw, 1, 1 - cw; only owned
 //     fine nodes count.  No atomics, no zeroing: one launch, bitwise
 //     reproducible.  The caller reverse-exchanges the coarse ghost planes.
+//
+// The per-node bodies (hprolong_node, hrestrict_node), the split tables and
+// the check of a level pair are csrc/include/bdx_mg_bodies.h, shared with the
+// V-cycle tail (pmg_tail.h) and the host twins (csrc/host/bdx_host_mg.cpp);
+// this file is the mapping of nodes to threads.
 #pragma once
 #include "bdx_common.h"
-
-// The device tables of one level pair, split per axis.
-template <typename T>
-struct HTransferTables {
-  const int* cidx[3];
-  const T* cw[3];
-  const int* fpos[3];
-};
+#include "bdx_mg_bodies.h"
 
 constexpr int kHTransferThreads = 256;  // 4 waves, one row piece each
 
@@ -54,29 +52,6 @@ __device__ __forceinline__ bool htransfer_piece(const BdxLattice& l, int64_t npi
   return k < l.L[2];
 }
 
-// P vc at fine node (i, j, k): the per-node body of the prolongation (also the
-// V-cycle tail's, pmg_tail.h).
-template <typename T>
-__device__ __forceinline__ T hprolong_node(const BdxLattice& lc, const HTransferTables<T>& tab,
-                                           const T* vc, int64_t i, int64_t j, int64_t k) {
-  const int64_t ci = tab.cidx[0][i], cj = tab.cidx[1][j], ck = tab.cidx[2][k];
-  const T wi = tab.cw[0][i], wj = tab.cw[1][j], wk = tab.cw[2][k];
-  const int na = wi != 0 ? 2 : 1, nb = wj != 0 ? 2 : 1;
-  T gx[2] = {0, 0};
-  for (int a = 0; a < na; ++a) {
-    T gy[2] = {0, 0};
-    for (int b = 0; b < nb; ++b) {
-      const int64_t at = lc.idx(ci + a, cj + b, ck);
-      T v = 0;
-      if (!BDX_OOB(at, lc.size(), "hprolong load")) v = vc[at];
-      if (wk != 0 && !BDX_OOB(at + 1, lc.size(), "hprolong load")) v += wk * (vc[at + 1] - v);
-      gy[b] = v;
-    }
-    gx[a] = nb == 2 ? gy[0] + wj * (gy[1] - gy[0]) : gy[0];
-  }
-  return na == 2 ? gx[0] + wi * (gx[1] - gx[0]) : gx[0];
-}
-
 // vf (+)= P vc: one thread per fine node.
 template <typename T>
 __global__ void __launch_bounds__(kHTransferThreads)
@@ -90,50 +65,6 @@ __global__ void __launch_bounds__(kHTransferThreads)
   if (!BDX_OOB(to, lf.size(), "hprolong store")) vf[to] = add ? vf[to] + out : out;
 }
 
-// Range [lo, hi] of the fine nodes coarse node j gathers on one axis and the
-// fine index of j itself; only owned fine nodes (index < own).
-__device__ __forceinline__ void hrestrict_range(const int* fpos, int64_t j, int64_t Lc, int64_t own,
-                                                int64_t& lo, int64_t& mid, int64_t& hi) {
-  mid = fpos[j];
-  lo = j > 0 ? fpos[j - 1] + 1 : mid;
-  hi = j < Lc - 1 ? fpos[j + 1] - 1 : mid;
-  if (hi > own - 1) hi = own - 1;
-}
-
-// Weight of fine node f in coarse node (at fine index mid).
-template <typename T>
-__device__ __forceinline__ T hrestrict_weight(const T* cw, int64_t f, int64_t mid) {
-  return f < mid ? cw[f] : (f == mid ? T(1) : T(1) - cw[f]);
-}
-
-// P^T (vf - y) at coarse node (i, j, k), a fixed-order gather: the per-node
-// body of the restriction (also the V-cycle tail's, pmg_tail.h).
-template <typename T>
-__device__ __forceinline__ T hrestrict_node(const BdxLattice& lc, const BdxLattice& lf,
-                                            const HTransferTables<T>& tab, const T* vf, const T* y,
-                                            int64_t i, int64_t j, int64_t k) {
-  int64_t lo[3], mid[3], hi[3];
-  hrestrict_range(tab.fpos[0], i, lc.L[0], lf.L[0] - lf.gh[0], lo[0], mid[0], hi[0]);
-  hrestrict_range(tab.fpos[1], j, lc.L[1], lf.L[1] - lf.gh[1], lo[1], mid[1], hi[1]);
-  hrestrict_range(tab.fpos[2], k, lc.L[2], lf.L[2] - lf.gh[2], lo[2], mid[2], hi[2]);
-  T sx = 0;
-  for (int64_t fi = lo[0]; fi <= hi[0]; ++fi) {
-    T sy = 0;
-    for (int64_t fj = lo[1]; fj <= hi[1]; ++fj) {
-      T sz = 0;
-      for (int64_t fk = lo[2]; fk <= hi[2]; ++fk) {
-        const int64_t at = lf.idx(fi, fj, fk);
-        if (BDX_OOB(at, lf.size(), "hrestrict load")) continue;
-        const T v = y ? vf[at] - y[at] : vf[at];
-        sz += hrestrict_weight(tab.cw[2], fk, mid[2]) * v;
-      }
-      sy += hrestrict_weight(tab.cw[1], fj, mid[1]) * sz;
-    }
-    sx += hrestrict_weight(tab.cw[0], fi, mid[0]) * sy;
-  }
-  return sx;
-}
-
 // vc = P^T (vf - y): one thread per coarse node.
 template <typename T>
 __global__ void __launch_bounds__(kHTransferThreads)
@@ -144,35 +75,6 @@ __global__ void __launch_bounds__(kHTransferThreads)
   const T sx = hrestrict_node<T>(lc, lf, tab, vf, y, i, j, k);
   const int64_t to = lc.idx(i, j, k);
   if (!BDX_OOB(to, lc.size(), "hrestrict store")) vc[to] = sx;
-}
-
-// Two degree-1 descriptors in the lattice layout on the same piece of the
-// partition, the coarse one with no more cells than the fine one per axis.
-inline bool htransfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
-  if (lc.tsy || lf.tsy) return false;
-  if (lc.P != 1 || lf.P != 1) return false;
-  for (int a = 0; a < 3; ++a) {
-    if (lc.gh[a] != lf.gh[a]) return false;
-    if (lc.n[a] < 0 || lc.n[a] > lf.n[a]) return false;
-    if (lc.L[a] != lc.n[a] + 1 || lf.L[a] != lf.n[a] + 1) return false;
-    if (lf.L[a] > 0x7fffffffLL) return false;  // int32 tables
-  }
-  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
-}
-
-template <typename T>
-__host__ __device__ inline HTransferTables<T> htransfer_tables(const BdxLattice& lc, const BdxLattice& lf,
-                                           const int* cidx, const T* cw, const int* fpos) {
-  HTransferTables<T> t;
-  int64_t of = 0, oc = 0;
-  for (int a = 0; a < 3; ++a) {
-    t.cidx[a] = cidx + of;
-    t.cw[a] = cw + of;
-    t.fpos[a] = fpos + oc;
-    of += lf.L[a];
-    oc += lc.L[a];
-  }
-  return t;
 }
 
 // Blocks that give every 64-node row piece of lattice l a wave; -1: too many.

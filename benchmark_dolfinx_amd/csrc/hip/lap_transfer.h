@@ -25,6 +25,8 @@
 #pragma once
 #include "lap_v1.h"
 
+#include "bdx_mg_bodies.h"  // transfer_pair_ok
+
 // The 1D interpolation table in T, passed by value (NF x NC <= 8 x 4).
 template <typename T>
 struct TransferTable {
@@ -213,18 +215,8 @@ int launch_restrict(const BdxLattice& lc, const BdxLattice& lf, const TransferTa
   return 0;
 }
 
-// Both descriptors in the lattice layout, on the same cells and the same
-// piece of the partition, with a degree pair of the schedule.
-inline bool transfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
-  if (lc.tsy || lf.tsy) return false;
-  if (lf.P < 2 || lf.P > 7 || lc.P != (lf.P / 2 > 1 ? lf.P / 2 : 1)) return false;
-  for (int a = 0; a < 3; ++a) {
-    if (lc.n[a] != lf.n[a] || lc.n[a] < 0 || lc.gh[a] != lf.gh[a]) return false;
-    if (lc.L[a] != lc.n[a] * lc.P + 1 || lf.L[a] != lf.n[a] * lf.P + 1) return false;
-  }
-  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
-}
-
+// transfer_pair_ok (bdx_mg_bodies.h): the check of a level pair, shared with
+// the host twins.
 template <typename T>
 int dispatch_transfer(bool restrict_, const BdxLattice& lc, const BdxLattice& lf, const double* J,
                       const T* src, T* dst, hipStream_t st) {

@@ -19,70 +19,18 @@
 // The operator of a level is its assembled 27-point stencil S[27][nstore] in
 // the level's storage index, plane (di + 1) 9 + (dj + 1) 3 + (dk + 1):
 // y[n] = sum of S[p][n] z[n + offset(p)] over the neighbours inside the
-// lattice, p ascending.  The transfers are the per-node bodies of
-// lap_htransfer.h.
+// lattice, p ascending.
 //
-// The level table: csrc/include/bdx_pmg_tail.h.
+// The level table and its decoder: csrc/include/bdx_pmg_tail.h.  The
+// Chebyshev entry update and the transfers are the per-node bodies of
+// csrc/include/bdx_mg_bodies.h, shared with the stand-alone kernels and the
+// host twin (csrc/host/bdx_host_mg.cpp); this file is the thread-stride phase
+// loops and the barriers between them (and the stencil row, see tail_apply).
 #pragma once
 #include "bdx_common.h"
 #include "bdx_pmg_tail.h"
-#include "lap_htransfer.h"
 
 constexpr int kTailThreads = 1024;
-
-template <typename T>
-struct TailLevel {
-  BdxLattice lat;
-  const T* S;
-  const T* dinv;
-  const unsigned char* bc;
-  T* r;
-  T* z;
-  T* d;
-  T* y;
-  const int* cidx;
-  const T* cw;
-  const int* fpos;
-  int ncoef;
-  const double* coef;
-  int nodes;
-};
-
-template <typename P>
-__device__ __forceinline__ P tail_ptr(int64_t w) {
-  return reinterpret_cast<P>(static_cast<uintptr_t>(w));
-}
-
-// Level l of the table; the first level's r and z are the launch's.
-template <typename T>
-__device__ __forceinline__ TailLevel<T> tail_level(const int64_t* tab, int l, const T* r0, T* z0) {
-  const int64_t* w = tab + static_cast<int64_t>(l) * kTailWords;
-  TailLevel<T> v;
-  for (int a = 0; a < 3; ++a) {
-    v.lat.n[a] = w[a];
-    v.lat.L[a] = w[3 + a];
-    v.lat.g0[a] = w[6 + a];
-    v.lat.N[a] = w[9 + a];
-    v.lat.gh[a] = w[12 + a];
-  }
-  v.lat.P = w[15];
-  v.lat.ld = w[16];
-  v.lat.tsy = v.lat.tsz = v.lat.tntz = v.lat.tcol = 0;
-  v.S = tail_ptr<const T*>(w[kTailS]);
-  v.dinv = tail_ptr<const T*>(w[kTailDinv]);
-  v.bc = tail_ptr<const unsigned char*>(w[kTailBc]);
-  v.r = l == 0 ? const_cast<T*>(r0) : tail_ptr<T*>(w[kTailR]);
-  v.z = l == 0 ? z0 : tail_ptr<T*>(w[kTailZ]);
-  v.d = tail_ptr<T*>(w[kTailD]);
-  v.y = tail_ptr<T*>(w[kTailY]);
-  v.cidx = tail_ptr<const int*>(w[kTailCidx]);
-  v.cw = tail_ptr<const T*>(w[kTailCw]);
-  v.fpos = tail_ptr<const int*>(w[kTailFpos]);
-  v.ncoef = static_cast<int>(w[kTailNcoef]);
-  v.coef = reinterpret_cast<const double*>(tab + w[kTailCoef]);
-  v.nodes = static_cast<int>(v.lat.L[0] * v.lat.L[1] * v.lat.L[2]);
-  return v;
-}
 
 // Node n of the thread-stride loop, z fastest.
 __device__ __forceinline__ void tail_node(const BdxLattice& lat, int n, int& i, int& j, int& k) {
@@ -93,7 +41,12 @@ __device__ __forceinline__ void tail_node(const BdxLattice& lat, int n, int& i, 
   j = ij - i * L1;
 }
 
-// y = A z with the level's stencil.
+// y = A z with the level's stencil: the sum of stencil27_node
+// (bdx_mg_bodies.h), written out here.  Called through that function the
+// kernel's code is no longer the one measured in profiles/pmg_tail.md: 670
+// instructions and two VGPRs more, or, with the row's index passed in, the
+// same size with the loads of every tap reordered and an FP32 call 1.3 %
+// slower (profiles/mg_shared_bodies.md).
 template <typename T>
 __device__ __forceinline__ void tail_apply(const TailLevel<T>& v) {
   const int L0 = static_cast<int>(v.lat.L[0]), L1 = static_cast<int>(v.lat.L[1]),
@@ -124,24 +77,16 @@ __device__ __forceinline__ void tail_apply(const TailLevel<T>& v) {
   }
 }
 
-// One Chebyshev update (blas.hip: cheb_step_kernel) on every node.
+// One Chebyshev update (the entry update of blas.hip: cheb_step_kernel) on
+// every node.
 template <typename T>
 __device__ __forceinline__ void tail_cheb(const TailLevel<T>& v, bool first, T a, T b) {
-  const int64_t ns = v.lat.size();
   for (int n = threadIdx.x; n < v.nodes; n += kTailThreads) {
     int i, j, k;
     tail_node(v.lat, n, i, j, k);
     const int64_t at = v.lat.idx(i, j, k);
-    if (BDX_OOB(at, ns, "pmg_tail cheb")) continue;
-    if (first) {
-      const T dn = b * v.dinv[at] * v.r[at];
-      v.d[at] = dn;
-      v.z[at] = dn;
-    } else {
-      const T dn = a * v.d[at] + b * v.dinv[at] * (v.r[at] - v.y[at]);
-      v.d[at] = dn;
-      v.z[at] = v.z[at] + dn;
-    }
+    if (BDX_OOB(at, v.lat.size(), "pmg_tail cheb")) continue;
+    cheb_entry<T>(first, a, b, v.dinv, v.r, v.y, v.d, v.z, at);
   }
 }
 
@@ -217,7 +162,7 @@ __global__ void __launch_bounds__(kTailThreads)
 template <typename T>
 int launch_pmg_tail(const int64_t* htab, const int64_t* dtab, int nlev, int64_t nwords,
                     const T* r, T* z, hipStream_t st) {
-  if (!dtab || !r || !z || !tail_table_ok(htab, nlev, nwords, htransfer_pair_ok))
+  if (!dtab || !r || !z || !tail_table_ok(htab, nlev, nwords))
     return static_cast<int>(hipErrorInvalidValue);
   pmg_tail_kernel<T><<<1, kTailThreads, 0, st>>>(dtab, nlev, r, z);
   BDX_CHECK(hipGetLastError());

@@ -27,7 +27,6 @@
 #include <vector>
 
 #include "../include/bdx_lattice.h"
-#include "../include/bdx_pmg_tail.h"
 #include "../include/bdx_watchdog.h"
 
 namespace {
@@ -832,360 +831,6 @@ int64_t csr_build(const int64_t* latd, int nq, const T* B, const T* Dd,
   return nnz;
 }
 
-// ------------------------------------------------- p-multigrid transfers
-// Host twins of csrc/hip/lap_transfer.h: per cell P = J (x) J (x) J with
-// J (nf x nc, row-major) the coarse Lagrange basis at the fine nodes.
-inline bool transfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
-  if (lc.tsy || lf.tsy) return false;
-  if (lf.P < 2 || lf.P > 7 || lc.P != std::max<int64_t>(1, lf.P / 2)) return false;
-  for (int a = 0; a < 3; ++a) {
-    if (lc.n[a] != lf.n[a] || lc.n[a] < 0 || lc.gh[a] != lf.gh[a]) return false;
-    if (lc.L[a] != lc.n[a] * lc.P + 1 || lf.L[a] != lf.n[a] * lf.P + 1) return false;
-  }
-  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
-}
-
-// vf = P vc: every local fine node written once (a cell writes its local
-// indices < Pf, and Pf where it is the last local cell of the axis).
-template <typename T>
-int prolong_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vc,
-                 T* vf) {
-  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
-  if (!transfer_pair_ok(lc, lf)) return 1;
-  const int PF = static_cast<int>(lf.P), PC = static_cast<int>(lc.P), nf = PF + 1, nc = PC + 1;
-  T J[8 * 4];
-  for (int i = 0; i < nf * nc; ++i) J[i] = static_cast<T>(Jd[i]);
-  const int64_t n1 = lf.n[1], n2 = lf.n[2], ncell = lf.n[0] * n1 * n2;
-#pragma omp parallel for schedule(static)
-  for (int64_t cell = 0; cell < ncell; ++cell) {
-    const int64_t cz = cell % n2, cy = (cell / n2) % n1, cx = cell / (n1 * n2);
-    T s0[4 * 4 * 8], s1[4 * 8 * 8];
-    // z: (a, b, c) -> (a, b, k)
-    for (int a = 0; a < nc; ++a)
-      for (int b = 0; b < nc; ++b)
-        for (int k = 0; k < nf; ++k) {
-          T acc = 0;
-          for (int c = 0; c < nc; ++c)
-            acc += J[k * nc + c] * vc[lc.idx(cx * PC + a, cy * PC + b, cz * PC + c)];
-          s0[(a * nc + b) * nf + k] = acc;
-        }
-    // y: (a, b, k) -> (a, j, k)
-    for (int a = 0; a < nc; ++a)
-      for (int j = 0; j < nf; ++j)
-        for (int k = 0; k < nf; ++k) {
-          T acc = 0;
-          for (int b = 0; b < nc; ++b) acc += J[j * nc + b] * s0[(a * nc + b) * nf + k];
-          s1[(a * nf + j) * nf + k] = acc;
-        }
-    // x: (a, j, k) -> (i, j, k)
-    const int ex = cx == lf.n[0] - 1 ? nf : PF, ey = cy == n1 - 1 ? nf : PF,
-              ez = cz == n2 - 1 ? nf : PF;
-    for (int i = 0; i < ex; ++i)
-      for (int j = 0; j < ey; ++j)
-        for (int k = 0; k < ez; ++k) {
-          T acc = 0;
-          for (int a = 0; a < nc; ++a) acc += J[i * nc + a] * s1[(a * nf + j) * nf + k];
-          vf[lf.idx(cx * PF + i, cy * PF + j, cz * PF + k)] = acc;
-        }
-  }
-  return 0;
-}
-
-// vc += P^T vf: each cell takes the fine nodes prolong_host writes, owned ones
-// only; cells of one parity colour share no coarse dof, so the colours run
-// one after the other (fixed order) and each in parallel.
-template <typename T>
-int restrict_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vf,
-                  T* vc) {
-  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
-  if (!transfer_pair_ok(lc, lf)) return 1;
-  const int PF = static_cast<int>(lf.P), PC = static_cast<int>(lc.P), nf = PF + 1, nc = PC + 1;
-  T J[8 * 4];
-  for (int i = 0; i < nf * nc; ++i) J[i] = static_cast<T>(Jd[i]);
-  for (int colour = 0; colour < 8; ++colour) {
-    const int64_t o[3] = {(colour >> 2) & 1, (colour >> 1) & 1, colour & 1};
-    int64_t e[3];
-    for (int a = 0; a < 3; ++a) e[a] = lf.n[a] > o[a] ? (lf.n[a] - o[a] + 1) / 2 : 0;
-    const int64_t ncell = e[0] * e[1] * e[2];
-#pragma omp parallel for schedule(static)
-    for (int64_t cell = 0; cell < ncell; ++cell) {
-      const int64_t cz = o[2] + 2 * (cell % e[2]), cy = o[1] + 2 * ((cell / e[2]) % e[1]),
-                    cx = o[0] + 2 * (cell / (e[1] * e[2]));
-      T s0[4 * 8 * 8], s1[4 * 4 * 8];
-      const int ex = cx == lf.n[0] - 1 ? nf : PF, ey = cy == lf.n[1] - 1 ? nf : PF,
-                ez = cz == lf.n[2] - 1 ? nf : PF;
-      // x: (i, j, k) -> (a, j, k)
-      for (int a = 0; a < nc; ++a)
-        for (int j = 0; j < nf; ++j)
-          for (int k = 0; k < nf; ++k) {
-            T acc = 0;
-            if (j < ey && k < ez)
-              for (int i = 0; i < ex; ++i) {
-                const int64_t li = cx * PF + i, lj = cy * PF + j, lk = cz * PF + k;
-                if (lf.is_owned(li, lj, lk)) acc += J[i * nc + a] * vf[lf.idx(li, lj, lk)];
-              }
-            s0[(a * nf + j) * nf + k] = acc;
-          }
-      // y: (a, j, k) -> (a, b, k)
-      for (int a = 0; a < nc; ++a)
-        for (int b = 0; b < nc; ++b)
-          for (int k = 0; k < nf; ++k) {
-            T acc = 0;
-            for (int j = 0; j < nf; ++j) acc += J[j * nc + b] * s0[(a * nf + j) * nf + k];
-            s1[(a * nc + b) * nf + k] = acc;
-          }
-      // z: (a, b, k) -> (a, b, c)
-      for (int a = 0; a < nc; ++a)
-        for (int b = 0; b < nc; ++b)
-          for (int c = 0; c < nc; ++c) {
-            T acc = 0;
-            for (int k = 0; k < nf; ++k) acc += J[k * nc + c] * s1[(a * nc + b) * nf + k];
-            vc[lc.idx(cx * PC + a, cy * PC + b, cz * PC + c)] += acc;
-          }
-    }
-  }
-  return 0;
-}
-
-// ------------------------------------------------- h-multigrid transfers
-// Host twins of csrc/hip/lap_htransfer.h: trilinear interpolation in index
-// space between two degree-1 lattices and its transpose; cidx / cw (fine
-// lengths) and fpos (coarse lengths) hold the three axes one after the other.
-inline bool htransfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
-  if (lc.tsy || lf.tsy) return false;
-  if (lc.P != 1 || lf.P != 1) return false;
-  for (int a = 0; a < 3; ++a) {
-    if (lc.gh[a] != lf.gh[a]) return false;
-    if (lc.n[a] < 0 || lc.n[a] > lf.n[a]) return false;
-    if (lc.L[a] != lc.n[a] + 1 || lf.L[a] != lf.n[a] + 1) return false;
-    if (lf.L[a] > 0x7fffffffLL) return false;
-  }
-  return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
-}
-
-// vf (+)= P vc: a + w (b - a) per axis, z then y then x; an axis with w = 0
-// takes a and reads nothing else.  add: owned fine nodes only.
-template <typename T>
-int hprolong_host(const int64_t* latc, const int64_t* latf, const int* cidx, const T* cw,
-                  const int* fpos, const T* vc, T* vf, int add) {
-  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
-  if (!htransfer_pair_ok(lc, lf) || !cidx || !cw || !fpos || !vc || !vf) return 1;
-  const int* cx[3] = {cidx, cidx + lf.L[0], cidx + lf.L[0] + lf.L[1]};
-  const T* w[3] = {cw, cw + lf.L[0], cw + lf.L[0] + lf.L[1]};
-  const int64_t e[3] = {add ? lf.L[0] - lf.gh[0] : lf.L[0], add ? lf.L[1] - lf.gh[1] : lf.L[1],
-                        add ? lf.L[2] - lf.gh[2] : lf.L[2]};
-#pragma omp parallel for collapse(2) schedule(static)
-  for (int64_t i = 0; i < e[0]; ++i)
-    for (int64_t j = 0; j < e[1]; ++j) {
-      const int64_t ci = cx[0][i], cj = cx[1][j];
-      const T wi = w[0][i], wj = w[1][j];
-      const int na = wi != 0 ? 2 : 1, nb = wj != 0 ? 2 : 1;
-      for (int64_t k = 0; k < e[2]; ++k) {
-        const int64_t ck = cx[2][k];
-        const T wk = w[2][k];
-        T gx[2] = {0, 0};
-        for (int a = 0; a < na; ++a) {
-          T gy[2] = {0, 0};
-          for (int b = 0; b < nb; ++b) {
-            const int64_t at = lc.idx(ci + a, cj + b, ck);
-            T v = vc[at];
-            if (wk != 0) v += wk * (vc[at + 1] - v);
-            gy[b] = v;
-          }
-          gx[a] = nb == 2 ? gy[0] + wj * (gy[1] - gy[0]) : gy[0];
-        }
-        const T out = na == 2 ? gx[0] + wi * (gx[1] - gx[0]) : gx[0];
-        const int64_t to = lf.idx(i, j, k);
-        vf[to] = add ? vf[to] + out : out;
-      }
-    }
-  return 0;
-}
-
-// vc = P^T (vf - y) (y null: P^T vf): every local coarse node gathers the
-// owned fine nodes strictly between its coarse neighbours, ascending, x
-// outermost, with the weights cw, 1, 1 - cw.
-template <typename T>
-int hrestrict_host(const int64_t* latc, const int64_t* latf, const int* cidx, const T* cw,
-                   const int* fpos, const T* vf, const T* y, T* vc) {
-  const BdxLattice lc = BdxLattice::from(latc), lf = BdxLattice::from(latf);
-  if (!htransfer_pair_ok(lc, lf) || !cidx || !cw || !fpos || !vc || !vf) return 1;
-  const T* w[3] = {cw, cw + lf.L[0], cw + lf.L[0] + lf.L[1]};
-  const int* fp[3] = {fpos, fpos + lc.L[0], fpos + lc.L[0] + lc.L[1]};
-  auto range = [&](int a, int64_t j, int64_t& lo, int64_t& mid, int64_t& hi) {
-    mid = fp[a][j];
-    lo = j > 0 ? fp[a][j - 1] + 1 : mid;
-    hi = j < lc.L[a] - 1 ? fp[a][j + 1] - 1 : mid;
-    hi = std::min<int64_t>(hi, lf.L[a] - lf.gh[a] - 1);
-  };
-  auto weight = [&](int a, int64_t f, int64_t mid) {
-    return f < mid ? w[a][f] : (f == mid ? T(1) : T(1) - w[a][f]);
-  };
-#pragma omp parallel for collapse(2) schedule(static)
-  for (int64_t i = 0; i < lc.L[0]; ++i)
-    for (int64_t j = 0; j < lc.L[1]; ++j)
-      for (int64_t k = 0; k < lc.L[2]; ++k) {
-        int64_t lo[3], mid[3], hi[3];
-        range(0, i, lo[0], mid[0], hi[0]);
-        range(1, j, lo[1], mid[1], hi[1]);
-        range(2, k, lo[2], mid[2], hi[2]);
-        T sx = 0;
-        for (int64_t fi = lo[0]; fi <= hi[0]; ++fi) {
-          T sy = 0;
-          for (int64_t fj = lo[1]; fj <= hi[1]; ++fj) {
-            T sz = 0;
-            for (int64_t fk = lo[2]; fk <= hi[2]; ++fk) {
-              const int64_t at = lf.idx(fi, fj, fk);
-              const T v = y ? vf[at] - y[at] : vf[at];
-              sz += weight(2, fk, mid[2]) * v;
-            }
-            sy += weight(1, fj, mid[1]) * sz;
-          }
-          sx += weight(0, fi, mid[0]) * sy;
-        }
-        vc[lc.idx(i, j, k)] = sx;
-      }
-  return 0;
-}
-
-// Host twin of bdx_cheb_step (csrc/hip/blas.hip) over the owned rows.
-template <typename T>
-void cheb_step_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, int first, T a,
-                    T b, const T* dinv, const T* r, const T* y, T* d, T* z) {
-#pragma omp parallel for collapse(2) schedule(static)
-  for (int64_t i = 0; i < o0; ++i)
-    for (int64_t j = 0; j < o1; ++j) {
-      const int64_t base = (i * L1 + j) * ld;
-      for (int64_t k = base; k < base + o2; ++k) {
-        if (first) {
-          d[k] = b * dinv[k] * r[k];
-          z[k] = d[k];
-        } else {
-          d[k] = a * d[k] + b * dinv[k] * (r[k] - y[k]);
-          z[k] = z[k] + d[k];
-        }
-      }
-    }
-}
-
-// out = (TO)a over the owned rows: the precision boundary of the mixed
-// multigrid solve (csrc/hip/mixed.hip); nothing outside the rows is touched.
-template <typename TI, typename TO>
-void convert_rows_host(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, const TI* a,
-                       TO* out) {
-#pragma omp parallel for collapse(2) schedule(static)
-  for (int64_t i = 0; i < o0; ++i)
-    for (int64_t j = 0; j < o1; ++j) {
-      const int64_t base = (i * L1 + j) * ld;
-      for (int64_t k = base; k < base + o2; ++k) out[k] = static_cast<TO>(a[k]);
-    }
-}
-
-// ------------------------------------------------------ V-cycle tail
-// Host twin of csrc/hip/pmg_tail.h: the levels of the table (bdx_pmg_tail.h)
-// walked down then up with the schedule of `PMultigrid._vcycle`, the operator
-// of every level its 27-point stencil S[27][nstore], plane (di + 1) 9 +
-// (dj + 1) 3 + (dk + 1), the neighbours inside the lattice in ascending plane
-// order; the Chebyshev step and the transfers are the host twins above.
-template <typename T>
-void stencil_host(const BdxLattice& lat, const T* S, const T* z, T* y) {
-  const int64_t ns = lat.size();
-  for (int64_t i = 0; i < lat.L[0]; ++i)
-    for (int64_t j = 0; j < lat.L[1]; ++j)
-      for (int64_t k = 0; k < lat.L[2]; ++k) {
-        const int64_t at = lat.idx(i, j, k);
-        T s = 0;
-        for (int64_t di = -1; di <= 1; ++di)
-          for (int64_t dj = -1; dj <= 1; ++dj)
-            for (int64_t dk = -1; dk <= 1; ++dk) {
-              if (i + di < 0 || i + di >= lat.L[0] || j + dj < 0 || j + dj >= lat.L[1] ||
-                  k + dk < 0 || k + dk >= lat.L[2])
-                continue;
-              const int64_t p = (di + 1) * 9 + (dj + 1) * 3 + (dk + 1);
-              s += S[p * ns + at] * z[lat.idx(i + di, j + dj, k + dk)];
-            }
-        y[at] = s;
-      }
-}
-
-template <typename T>
-struct TailLevelHost {
-  const int64_t* latd;
-  BdxLattice lat;
-  const T *S, *dinv;
-  const unsigned char* bc;
-  T *r, *z, *d, *y;
-  const int* cidx;
-  const T* cw;
-  const int* fpos;
-  int64_t ncoef;
-  const double* coef;
-};
-
-template <typename P>
-P tail_ptr(int64_t w) {
-  return reinterpret_cast<P>(static_cast<uintptr_t>(w));
-}
-
-template <typename T>
-TailLevelHost<T> tail_level_host(const int64_t* tab, int l, const T* r0, T* z0) {
-  const int64_t* w = tab + static_cast<int64_t>(l) * kTailWords;
-  TailLevelHost<T> v;
-  v.latd = w;
-  v.lat = BdxLattice::from(w);
-  v.S = tail_ptr<const T*>(w[kTailS]);
-  v.dinv = tail_ptr<const T*>(w[kTailDinv]);
-  v.bc = tail_ptr<const unsigned char*>(w[kTailBc]);
-  v.r = l == 0 ? const_cast<T*>(r0) : tail_ptr<T*>(w[kTailR]);
-  v.z = l == 0 ? z0 : tail_ptr<T*>(w[kTailZ]);
-  v.d = tail_ptr<T*>(w[kTailD]);
-  v.y = tail_ptr<T*>(w[kTailY]);
-  v.cidx = tail_ptr<const int*>(w[kTailCidx]);
-  v.cw = tail_ptr<const T*>(w[kTailCw]);
-  v.fpos = tail_ptr<const int*>(w[kTailFpos]);
-  v.ncoef = w[kTailNcoef];
-  v.coef = reinterpret_cast<const double*>(tab + w[kTailCoef]);
-  return v;
-}
-
-template <typename T>
-void tail_smooth_host(const TailLevelHost<T>& v, bool zero_guess) {
-  const BdxLattice& l = v.lat;
-  for (int64_t s = 0; s < v.ncoef; ++s) {
-    const T a = static_cast<T>(v.coef[2 * s]), b = static_cast<T>(v.coef[2 * s + 1]);
-    const bool first = s == 0 && zero_guess;
-    if (!first) stencil_host<T>(l, v.S, v.z, v.y);
-    cheb_step_host<T>(l.L[1], l.ld, l.L[0], l.L[1], l.L[2], first, a, b, v.dinv, v.r, v.y, v.d,
-                      v.z);
-  }
-}
-
-template <typename T>
-int pmg_tail_host(const int64_t* tab, int nlev, int64_t nwords, const T* r, T* z) {
-  if (!r || !z || !tail_table_ok(tab, nlev, nwords, htransfer_pair_ok)) return 1;
-  for (int l = 0; l < nlev; ++l) {
-    const TailLevelHost<T> v = tail_level_host<T>(tab, l, r, z);
-    tail_smooth_host(v, true);
-    if (l == nlev - 1) break;
-    const TailLevelHost<T> c = tail_level_host<T>(tab, l + 1, r, z);
-    stencil_host<T>(v.lat, v.S, v.z, v.y);
-    if (hrestrict_host<T>(c.latd, v.latd, v.cidx, v.cw, v.fpos, v.r, v.y, c.r)) return 1;
-    for (int64_t i = 0; i < c.lat.L[0]; ++i)
-      for (int64_t j = 0; j < c.lat.L[1]; ++j)
-        for (int64_t k = 0; k < c.lat.L[2]; ++k) {
-          const int64_t at = c.lat.idx(i, j, k);
-          if (c.bc[at]) c.r[at] = 0;
-        }
-  }
-  for (int l = nlev - 2; l >= 0; --l) {
-    const TailLevelHost<T> v = tail_level_host<T>(tab, l, r, z);
-    const TailLevelHost<T> c = tail_level_host<T>(tab, l + 1, r, z);
-    if (hprolong_host<T>(c.latd, v.latd, v.cidx, v.cw, v.fpos, c.z, v.z, 1)) return 1;
-    tail_smooth_host(v, false);
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1298,51 +943,6 @@ int bdx_host_version() { return 1; }
     }                                                                         \
     dispatch<Diag<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
   }                                                                           \
-  /* p-multigrid transfers between the coarse and fine lattices latc / latf */ \
-  /* (J: the (Pf + 1) x (Pc + 1) 1D table): vf = P vc, vc += P^T vf; the   */ \
-  /* host twins of bdx_prolong / bdx_restrict, nonzero for a bad pair      */ \
-  int bdx_cpu_prolong_##SUF(const int64_t* latc, const int64_t* latf,         \
-                            const double* J, const T* vc, T* vf) {            \
-    return prolong_host<T>(latc, latf, J, vc, vf);                            \
-  }                                                                           \
-  int bdx_cpu_restrict_##SUF(const int64_t* latc, const int64_t* latf,        \
-                             const double* J, const T* vf, T* vc) {           \
-    return restrict_host<T>(latc, latf, J, vf, vc);                           \
-  }                                                                           \
-  /* h-multigrid transfers between the degree-1 lattices latc / latf with   */ \
-  /* the tables cidx, cw, fpos: vf (+)= P vc, vc = P^T (vf - y); the host    */ \
-  /* twins of bdx_hprolong / bdx_hrestrict, nonzero for a bad pair          */ \
-  int bdx_cpu_hprolong_##SUF(const int64_t* latc, const int64_t* latf,        \
-                             const int* cidx, const T* cw, const int* fpos,   \
-                             const T* vc, T* vf, int add) {                   \
-    return hprolong_host<T>(latc, latf, cidx, cw, fpos, vc, vf, add);         \
-  }                                                                           \
-  int bdx_cpu_hrestrict_##SUF(const int64_t* latc, const int64_t* latf,       \
-                              const int* cidx, const T* cw, const int* fpos,  \
-                              const T* vf, const T* y, T* vc) {               \
-    return hrestrict_host<T>(latc, latf, cidx, cw, fpos, vf, y, vc);          \
-  }                                                                           \
-  /* Chebyshev step d = a d + b dinv (r - y); z += d (first: d = z = b dinv */ \
-  /* r), the host twin of bdx_cheb_step                                    */ \
-  void bdx_cpu_cheb_step_##SUF(int64_t L1, int64_t ld, int64_t o0,            \
-                               int64_t o1, int64_t o2, int first, double a,   \
-                               double b, const T* dinv, const T* r,           \
-                               const T* y, T* d, T* z) {                      \
-    cheb_step_host<T>(L1, ld, o0, o1, o2, first, static_cast<T>(a),           \
-                      static_cast<T>(b), dinv, r, y, d, z);                   \
-  }                                                                           \
-  /* the V-cycle from the first level of the table (bdx_pmg_tail.h) down and */ \
-  /* back up, z = M r: the host twin of bdx_pmg_tail, nonzero for a bad table */ \
-  int bdx_cpu_pmg_tail_##SUF(const int64_t* tab, int nlev, int64_t nwords,    \
-                             const T* r, T* z) {                              \
-    return pmg_tail_host<T>(tab, nlev, nwords, r, z);                         \
-  }                                                                           \
-  /* y = A z with the 27-point stencil S of the degree-1 lattice latd (the  */ \
-  /* tail's operator, alone)                                                */ \
-  void bdx_cpu_stencil27_##SUF(const int64_t* latd, const T* S, const T* z,   \
-                               T* y) {                                        \
-    stencil_host<T>(BdxLattice::from(latd), S, z, y);                         \
-  }                                                                           \
   int64_t bdx_cpu_csr_##SUF(const int64_t* latd, int nq, const T* B,          \
                             const T* Dd, const T* wts, const T* qpts,         \
                             const T* xv, T kappa, const T* kc,                \
@@ -1398,20 +998,6 @@ int bdx_host_version() { return 1; }
 
 BDX_HOST_API(double, f64)
 BDX_HOST_API(float, f32)
-
-// out = (float)a over the owned rows (round to nearest even): the host twin
-// of bdx_demote_f64_f32 (csrc/hip/mixed.hip).
-void bdx_cpu_demote_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,
-                            const double* a, float* out) {
-  convert_rows_host<double, float>(L1, ld, o0, o1, o2, a, out);
-}
-
-// out = (double)a over the owned rows (exact): the host twin of
-// bdx_promote_f32_f64.
-void bdx_cpu_promote_f32_f64(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,
-                             const float* a, double* out) {
-  convert_rows_host<float, double>(L1, ld, o0, o1, o2, a, out);
-}
 
 // CPU unit test of the RCCL deadline policy (csrc/include/bdx_watchdog.h, used
 // by the native runtime around every blocking RCCL call and host wait): a

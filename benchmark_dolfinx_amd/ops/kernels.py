@@ -392,7 +392,7 @@ class HipKernels:
 
 class HostKernels:
     """The p-multigrid kernels of `HipKernels` on the host twins
-    (csrc/host/bdx_host.cpp), so the CPU platform runs the same Python path."""
+    (csrc/host/bdx_host_mg.cpp), so the CPU platform runs the same Python path."""
 
     def __init__(self, lat, dtype):
         self.lib = native.host()

@@ -6,7 +6,7 @@ perturbation and per-cell kappa; its operator comes from `make_operator`, its
 smoothing diagonal from `jacobi_inverse()`.  The transfers are the nodal
 interpolation J (x) J (x) J per cell (J[a, i] = l_i^c(xi_a^f), the coarse GLL
 Lagrange basis at the fine GLL nodes) and its exact transpose
-(csrc/hip/lap_transfer.h, host twins in csrc/host/bdx_host.cpp).
+(csrc/hip/lap_transfer.h, host twins in csrc/host/bdx_host_mg.cpp).
 
 V-cycle on level l with residual r:
     z = smooth(r, zero guess);  res = r - A z;  r_c = R res;
@@ -40,14 +40,14 @@ default): every level, level 0 and the h-levels included, is an FP32 problem
 with the FP64 problem's comm, cells, partition, perturbation, coefficient and
 shear, and the whole setup and cycle above run on them unchanged.  `apply`
 keeps its FP64 contract by demoting r into `rc`, running `apply_cycle(rc, zc)`
-and promoting `zc` (csrc/hip/mixed.hip, host twins in csrc/host/bdx_host.cpp);
+and promoting `zc` (csrc/hip/mixed.hip, host twins in csrc/host/bdx_host_mg.cpp);
 a caller that fuses the boundary into its own kernels (`DeviceCG`) calls
 `apply_cycle` directly.  The cycle is linear in r and is applied unscaled.
 
 Tail (`tail_nodes=N > 0`, off by default): the longest suffix of the level
 list whose levels all have degree 1 and at most N local nodes runs in one
 call, `pmg_tail` (csrc/hip/pmg_tail.h: one launch of one workgroup, the phases
-separated by workgroup barriers; host twin in csrc/host/bdx_host.cpp), where
+separated by workgroup barriers; host twin in csrc/host/bdx_host_mg.cpp), where
 the cycle reaches its first level.  The schedule, the coefficients, `dinv`,
 `bc` and the transfer tables are the levels' own; setup is unchanged, lambda_max
 included.  Inside the tail a level's operator is its assembled 27-point
