@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "bdx_debug.h"  // BDX_DASSERT, BDX_OOB: the BDX_DEBUG=1 index checks
+#include "bdx_hip_api.h"  // every entry point's prototype, ahead of its definition
 #include "bdx_lattice.h"
 
 #define BDX_CHECK(expr)                                                     \

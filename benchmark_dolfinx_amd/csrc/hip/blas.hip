@@ -264,19 +264,14 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
 }
 
 #define BDX_BLAS_API(T, SUF)                                                  \
-  int bdx_dot_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, \
-                    const T* a, const T* b, double* partials, double* out,    \
-                    int slot, hipStream_t st) {                               \
+  int bdx_dot_##SUF BDX_P_DOT(T) {                                            \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
     dot_rows_kernel<T, T><<<g, kBlock, 0, st>>>(s, a, b, partials);           \
     reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials, g, out, slot);     \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  int bdx_cg_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,     \
-                          int64_t o2, T* x, T* r, const T* p, const T* y,     \
-                          double* scal, int rn_slot, int pap_slot,            \
-                          int out_slot, double* partials, hipStream_t st) {   \
+  int bdx_cg_update_##SUF BDX_P_CG_UPDATE(T) {                                \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
     cg_update_kernel<T, false><<<g, kBlock, 0, st>>>(                         \
@@ -284,20 +279,13 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
     reduce_partials_kernel<<<1, kBlock, 0, st>>>(partials, g, scal, out_slot); \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  int bdx_p_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,      \
-                         int64_t o2, T* p, const T* r, const double* scal,    \
-                         int num, int den, hipStream_t st) {                  \
+  int bdx_p_update_##SUF BDX_P_P_UPDATE(T) {                                  \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     p_update_kernel<T, T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(         \
         s, p, r, scal, num, den);                                             \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  /* Jacobi PCG update: r.z -> scal[out_slot], r.r -> scal[rr_slot] */        \
-  int bdx_pcg_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,    \
-                           int64_t o2, T* x, T* r, const T* p, const T* y,    \
-                           const T* dinv, double* scal, int rz_slot,          \
-                           int pap_slot, int out_slot, int rr_slot,           \
-                           double* partials, hipStream_t st) {                \
+  int bdx_pcg_update_##SUF BDX_P_PCG_UPDATE(T) {                              \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
     pcg_update_kernel<T><<<g, kBlock, 0, st>>>(s, x, r, p, y, dinv, scal,     \
@@ -307,21 +295,13 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
                                                  rr_slot);                    \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  int bdx_pcg_p_update_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,  \
-                             int64_t o2, T* p, const T* r, const T* dinv,     \
-                             const double* scal, int num, int den,            \
-                             hipStream_t st) {                                \
+  int bdx_pcg_p_update_##SUF BDX_P_PCG_P_UPDATE(T) {                          \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     pcg_p_update_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(        \
         s, p, r, dinv, scal, num, den);                                       \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  /* Chebyshev step: d = a d + b dinv (r - y); z += d (first: d = z = b */    \
-  /* dinv r; y may then be null) */                                           \
-  int bdx_cheb_step_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,     \
-                          int64_t o2, int first, double a, double b,          \
-                          const T* dinv, const T* r, const T* y, T* d, T* z,  \
-                          hipStream_t st) {                                   \
+  int bdx_cheb_step_##SUF BDX_P_CHEB_STEP(T) {                                \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     const int g = grid_for_rows(o0 * o1);                                     \
     if (first)                                                                \
@@ -332,31 +312,22 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
           s, static_cast<T>(a), static_cast<T>(b), dinv, r, y, d, z);         \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  int bdx_axpy_##SUF(int64_t L1, int64_t ld, int64_t o0, int64_t o1,          \
-                     int64_t o2, T* out, double alpha, const T* x, const T* y, \
-                     hipStream_t st) {                                        \
+  int bdx_axpy_##SUF BDX_P_AXPY(T) {                                          \
     RowSpace s{L1, ld, o0, o1, o2};                                           \
     axpy_kernel<T><<<grid_for_rows(o0 * o1), kBlock, 0, st>>>(                \
         s, out, static_cast<T>(alpha), x, y);                                 \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  int bdx_box_copy_##SUF(int mode, T* vec, int64_t L1, int64_t ld,            \
-                         const int64_t* boxes, int nboxes, int64_t total,     \
-                         T* buf, hipStream_t st) {                            \
+  int bdx_box_copy_##SUF BDX_P_BOX_COPY(T) {                                  \
     const VecIdx vi{L1, ld, 0, 0, 0, 0};                                      \
     return box_copy_vi<T>(mode, vec, vi, boxes, nboxes, total, buf, st);      \
   }                                                                           \
-  /* the same on a lattice descriptor (lattice or tiled storage) */           \
-  int bdx_box_copy_lat_##SUF(int mode, T* vec, const int64_t* latd,           \
-                             const int64_t* boxes, int nboxes, int64_t total, \
-                             T* buf, hipStream_t st) {                        \
+  int bdx_box_copy_lat_##SUF BDX_P_BOX_COPY_LAT(T) {                          \
     const BdxLattice L = BdxLattice::from(latd);                              \
     const VecIdx vi{L.L[1], L.ld, L.tsy, L.tsz, L.tntz, L.tcol};              \
     return box_copy_vi<T>(mode, vec, vi, boxes, nboxes, total, buf, st);      \
   }                                                                           \
-  /* lattice <-> tiled copy of a vector (dir 0: to tiled, 1: back) */         \
-  int bdx_layout_convert_##SUF(int dir, const int64_t* latd_tiled, T* lat,    \
-                               T* tiled, hipStream_t st) {                    \
+  int bdx_layout_convert_##SUF BDX_P_LAYOUT_CONVERT(T) {                      \
     const BdxLattice L = BdxLattice::from(latd_tiled);                        \
     if (!L.tsy) return static_cast<int>(hipErrorInvalidValue);                \
     const VecIdx lv{L.L[1], L.ld, 0, 0, 0, 0};                                \
@@ -368,13 +339,7 @@ int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
                                                    L.L[2], lat, tiled);       \
     return static_cast<int>(hipGetLastError());                               \
   }                                                                           \
-  /* tiled x += a1 p1 [+ a2 p2], exported to the lattice layout (p2 may be */ \
-  /* null; p2mask bits 0-1: tile colours that take it, bit 2: export only, */ \
-  /* the tiled iterate keeps its lagged terms pending) */                     \
-  int bdx_flush_export_##SUF(const int64_t* latd_tiled, T* lat, T* tiled,     \
-                             const T* p1, const T* p2, const double* scal,    \
-                             int num1, int den1, int num2, int den2,          \
-                             int p2mask, hipStream_t st) {                    \
+  int bdx_flush_export_##SUF BDX_P_FLUSH_EXPORT(T) {                          \
     const BdxLattice L = BdxLattice::from(latd_tiled);                        \
     if (!L.tsy || (L.tsy * L.tsz * static_cast<int64_t>(sizeof(T))) % 16)    \
       return static_cast<int>(hipErrorInvalidValue);                          \

@@ -90,7 +90,3 @@ __global__ void __launch_bounds__(kBlock)
 }
 
 }  // namespace bdx_rows
-
-// blas.hip: fixed-order sum of n per-block partials into out[slot]
-extern "C" int bdx_reduce_partials(const double* partials, int n, double* out, int slot,
-                                   hipStream_t st);

@@ -536,14 +536,23 @@ static int rows_grid(int64_t nrows) {
   return static_cast<int>(want < 2048 ? (want > 0 ? want : 1) : 2048);
 }
 
+// Fixed-order sum of the g block partials of an update pass into scal[slot]
+// (two stages above 4 kStage1 partials).
+static void reduce_update_partials(double* partials, int g, double* scal, int slot,
+                                   hipStream_t st) {
+  if (g > 4 * kStage1) {
+    double* stage = partials + kPartialsCap - kStage1;
+    reduce_partials_slices<<<kStage1, 256, 0, st>>>(partials, g, stage);
+    reduce_partials_fixed<<<1, 256, 0, st>>>(stage, kStage1, scal, slot);
+  } else {
+    reduce_partials_fixed<<<1, 256, 0, st>>>(partials, g, scal, slot);
+  }
+}
+
 extern "C" {
 
 #define BDX_CGI(T, SUF)                                                              \
-  int bdx_cg_update_iface_##SUF(const int64_t* latd, const int64_t* own, T* r,      \
-                                const T* y, const T* yb, const T* zb, const T* cb,  \
-                                int nty, int ntz, int sy, int sz, double* scal,     \
-                                int rn_slot, int pap_slot, int out_slot,            \
-                                double* partials, hipStream_t st) {                 \
+  int bdx_cg_update_iface_##SUF BDX_P_CG_UPDATE_IFACE(T) {                          \
     const BdxLattice lat = BdxLattice::from(latd);                                  \
     int g;                                                                          \
     {                                                             \
@@ -555,17 +564,10 @@ extern "C" {
                                                   nty, ntz, sy, sz, scal, rn_slot,  \
                                                   pap_slot, partials);              \
     }                                                                               \
-    if (g > 4 * kStage1) {                                                          \
-      double* stage = partials + kPartialsCap - kStage1;                            \
-      reduce_partials_slices<<<kStage1, 256, 0, st>>>(partials, g, stage);          \
-      reduce_partials_fixed<<<1, 256, 0, st>>>(stage, kStage1, scal, out_slot);     \
-    } else {                                                                        \
-      reduce_partials_fixed<<<1, 256, 0, st>>>(partials, g, scal, out_slot);        \
-    }                                                                               \
+    reduce_update_partials(partials, g, scal, out_slot, st);                        \
     return static_cast<int>(hipGetLastError());                                     \
   }                                                                                 \
-  int bdx_xflush_##SUF(const int64_t* latd, const int64_t* own, T* x, const T* p,   \
-                       const double* scal, int num, int den, hipStream_t st) {      \
+  int bdx_xflush_##SUF BDX_P_XFLUSH(T) {                                            \
     const BdxLattice lat = BdxLattice::from(latd);                                  \
     xflush_kernel<T><<<rows_grid(own[0] * own[1]), 256, 0, st>>>(                   \
         lat.L[1], lat.ld, own[0], own[1], own[2], x, p, scal, num, den);            \
@@ -575,13 +577,8 @@ BDX_CGI(double, f64)
 BDX_CGI(float, f32)
 #undef BDX_CGI
 
-// Tiled-storage variants of the r update and the x flush (latd: the tiled
-// descriptor of bdx_lattice.h).
 #define BDX_CGT(T, SUF)                                                                         \
-  int bdx_cg_update_tiled_##SUF(const int64_t* latd, const int64_t* own, T* r, const T* y,     \
-                                const T* yb, const T* zb, const T* cb, int nty, int ntz,       \
-                                double* scal, int rn_slot, int pap_slot, int out_slot,         \
-                                double* partials, hipStream_t st) {                            \
+  int bdx_cg_update_tiled_##SUF BDX_P_CG_UPDATE_TILED(T) {                                     \
     const BdxLattice L = BdxLattice::from(latd);                                               \
     if (!L.tsy || (L.tsy * L.tsz * static_cast<int64_t>(sizeof(T))) % 16)                     \
       return static_cast<int>(hipErrorInvalidValue);                                           \
@@ -615,13 +612,7 @@ BDX_CGI(float, f32)
           L.L[0], L.L[1], L.L[2], static_cast<int>(L.tsy), static_cast<int>(L.tsz),            \
           static_cast<int>(L.tntz), own[0], own[1], own[2], nvec, r, y, yb, zb, cb, nty, ntz,  \
           scal, rn_slot, pap_slot, partials);                                                  \
-    if (g > 4 * kStage1) {                                                                     \
-      double* stage = partials + kPartialsCap - kStage1;                                       \
-      reduce_partials_slices<<<kStage1, 256, 0, st>>>(partials, g, stage);                     \
-      reduce_partials_fixed<<<1, 256, 0, st>>>(stage, kStage1, scal, out_slot);                \
-    } else {                                                                                   \
-      reduce_partials_fixed<<<1, 256, 0, st>>>(partials, g, scal, out_slot);                   \
-    }                                                                                          \
+    reduce_update_partials(partials, g, scal, out_slot, st);                                   \
     return static_cast<int>(hipGetLastError());                                                \
   }
 BDX_CGT(double, f64)
@@ -630,33 +621,10 @@ BDX_CGT(float, f32)
 
 }  // extern "C"
 
-// Fixed-order sum of the g block partials of an update pass into scal[slot]
-// (the two-stage scheme of the unpreconditioned entry points above).
-static void reduce_update_partials(double* partials, int g, double* scal, int slot,
-                                   hipStream_t st) {
-  if (g > 4 * kStage1) {
-    double* stage = partials + kPartialsCap - kStage1;
-    reduce_partials_slices<<<kStage1, 256, 0, st>>>(partials, g, stage);
-    reduce_partials_fixed<<<1, 256, 0, st>>>(stage, kStage1, scal, slot);
-  } else {
-    reduce_partials_fixed<<<1, 256, 0, st>>>(partials, g, scal, slot);
-  }
-}
-
 extern "C" {
 
-// Jacobi-preconditioned r update of the fused CG loop, lattice layout:
-// bdx_cg_update_iface_* (same fold, same r, bit for bit) plus z = dinv . r
-// stored for every vector r is stored for, r.z -> scal[out_slot] and
-// r.r -> scal[rr_slot] over the owned nodes.  partials_rr: a second buffer of
-// bdx_hip_partials_size() doubles; both sums are reduced in fixed order.
 #define BDX_PCGI(T, SUF)                                                                  \
-  int bdx_pcg_update_iface_##SUF(const int64_t* latd, const int64_t* own, T* r,          \
-                                 const T* y, const T* yb, const T* zb, const T* cb,      \
-                                 int nty, int ntz, int sy, int sz, double* scal,         \
-                                 int rn_slot, int pap_slot, int out_slot,                \
-                                 double* partials, const T* dinv, T* z, int rr_slot,     \
-                                 double* partials_rr, hipStream_t st) {                  \
+  int bdx_pcg_update_iface_##SUF BDX_P_PCG_UPDATE_IFACE(T) {                             \
     if (!dinv || !z || !partials_rr || partials_rr == partials || rr_slot == out_slot)   \
       return static_cast<int>(hipErrorInvalidValue);                                     \
     const BdxLattice lat = BdxLattice::from(latd);                                       \
@@ -674,15 +642,8 @@ BDX_PCGI(double, f64)
 BDX_PCGI(float, f32)
 #undef BDX_PCGI
 
-// The same on the tiled storage (latd: the tiled descriptor; dinv and z in
-// tiled storage too): the kernel selection of bdx_cg_update_tiled_* -- the
-// BDX_UPD_PLAIN hook and the 31-bit guard of the prefetching kernel included.
 #define BDX_PCGT(T, SUF)                                                                        \
-  int bdx_pcg_update_tiled_##SUF(const int64_t* latd, const int64_t* own, T* r, const T* y,    \
-                                 const T* yb, const T* zb, const T* cb, int nty, int ntz,      \
-                                 double* scal, int rn_slot, int pap_slot, int out_slot,        \
-                                 double* partials, const T* dinv, T* z, int rr_slot,           \
-                                 double* partials_rr, hipStream_t st) {                        \
+  int bdx_pcg_update_tiled_##SUF BDX_P_PCG_UPDATE_TILED(T) {                                   \
     if (!dinv || !z || !partials_rr || partials_rr == partials || rr_slot == out_slot)         \
       return static_cast<int>(hipErrorInvalidValue);                                           \
     const BdxLattice L = BdxLattice::from(latd);                                               \
@@ -733,9 +694,7 @@ int bdx_fused_tile(int nq, int* ty, int* tz) {
 }
 
 #define BDX_FIN(T, SUF)                                                          \
-  int bdx_fused_finalize_##SUF(const int64_t* latd, T* y, const T* yb, const T* zb, \
-                               const T* cb, int nty, int ntz, int sy, int sz,      \
-                               int ghost_only, hipStream_t st) {                   \
+  int bdx_fused_finalize_##SUF BDX_P_FUSED_FINALIZE(T) {                           \
     const BdxLattice lat = BdxLattice::from(latd);                                 \
     if (ghost_only) {                                                              \
       const int64_t Lx = lat.L[0], Ly = lat.L[1], Lz = lat.L[2];                   \
@@ -762,8 +721,7 @@ BDX_FIN(double, f64)
 BDX_FIN(float, f32)
 
 #define BDX_TABS(T, SUF)                                                           \
-  int bdx_fused_tables_##SUF(int nd, int nq, const double* phi0, const double* dphi1, \
-                             T* out) {                                             \
+  int bdx_fused_tables_##SUF BDX_P_FUSED_TABLES(T) {                               \
     switch (nd * 16 + nq) {                                                        \
       case 2 * 16 + 2: return pack_tables<T, 2, 2>(phi0, dphi1, out);              \
       case 2 * 16 + 3: return pack_tables<T, 2, 3>(phi0, dphi1, out);              \
@@ -786,8 +744,7 @@ BDX_TABS(double, f64)
 BDX_TABS(float, f32)
 
 #define BDX_TABS3(T, SUF)                                                          \
-  int bdx_fused3_tables_##SUF(int nd, int nq, const double* phi0, const double* Dd, \
-                              T* out) {                                            \
+  int bdx_fused3_tables_##SUF BDX_P_FUSED3_TABLES(T) {                             \
     switch (nd * 16 + nq) {                                                        \
       case 2 * 16 + 3: return pack_tables3<T, 2, 3>(phi0, Dd, out);                \
       case 3 * 16 + 4: return pack_tables3<T, 3, 4>(phi0, Dd, out);                \

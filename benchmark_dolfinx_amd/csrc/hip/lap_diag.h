@@ -205,16 +205,8 @@ int dispatch_diag(int P, int nq, const BdxLattice& lat, const OpTables<T>& tb, c
   return static_cast<int>(hipErrorInvalidValue);
 }
 
-// d += diag(A) contributions of the cells [lo, hi) of the local lattice
-// (d: lattice layout, zeroed by the caller; Dirichlet dofs are left alone).
-// `identity` is taken only to keep the table arguments of bdx_v1_apply; the
-// kernel does not use it (phi0 = I runs through the general contraction).
 #define BDX_DIAG_API(T, SUF)                                                           \
-  extern "C" int bdx_diag_##SUF(const int64_t* latd, int nq, const double* phi0,       \
-                                const double* dphi1, const double* wts,                \
-                                const double* qpts, int identity, const T* xv,         \
-                                double kappa, const T* kc, T* d, const int64_t* lo,    \
-                                const int64_t* hi, hipStream_t st) {                   \
+  extern "C" int bdx_diag_##SUF BDX_P_DIAG(T) {                                        \
     const BdxLattice lat = BdxLattice::from(latd);                                     \
     if (lat.tsy) return static_cast<int>(hipErrorInvalidValue);                        \
     for (int a = 0; a < 3; ++a)                                                        \

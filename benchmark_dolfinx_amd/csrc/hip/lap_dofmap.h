@@ -864,8 +864,7 @@ __global__ void __launch_bounds__(DofShape<NQ>::NT)
 // (nd <= 8, nq <= 8): the MFMA one (lap_dofmfma.h) or the line-per-lane VALU
 // one above.  BDX_DOFMAP_MFMA=1 / 0 forces it (A/B builds and tests); unset:
 // kDofMfmaDefault(nq).  bdx_dofmap_set_mfma() overrides both (-1: back to
-// the environment / default).
-extern "C" int bdx_dofmap_set_mfma(int mode);
+// the environment / default).  Not part of the C ABI (lap_dofmap_f64.hip).
 int bdx_dofmap_mfma_mode();
 // Round 6, same box, bench.py --kernel dofmap --geometry stored, GDoF/s (VALU
 // / MFMA): Q3 14.47 / 10.74, Q6 22.79 / 21.31 (profiles/r6_dofmap_mfma.md):
@@ -1054,33 +1053,15 @@ int launch_dofmap_geometry(int ncells, const int* cverts, const T* coords, const
   return static_cast<int>(hipGetLastError());
 }
 
-// apply: mode 0 = action (u -> y += A u), 1 = CG operator (u = r); returns the
-// number of p.Ap partials written at partials (CG) in *nblocks.
+// The dofmap entry points of one scalar type (bdx_hip_api.h).
 #define BDX_DOFMAP_API(T, SUF)                                                                    \
-  extern "C" int bdx_dofmap_apply_yz_##SUF(                                                       \
-      int, int, int, int, const T*, const int*, int, int64_t, const int*, const int*, const T*,   \
-      const unsigned char*, const T*, double, const T*, const T*, const T*, T*, T*, T*, T*,       \
-      const double*, int, int, int, int, double*, int*, hipStream_t);                             \
-  extern "C" int bdx_dofmap_cg_update_z_##SUF(int64_t, const unsigned char*, T*, T*,              \
-                                              const double*, int, int, double*, int*, int,        \
-                                              hipStream_t);                                       \
-  extern "C" int bdx_dofmap_apply_##SUF(                                                          \
-      int P, int nq, int geom, int mode, const T* tab, const int* cells, int ncl, int64_t nvec,   \
-      const int* cdofs, const int* cverts, const T* coords, const unsigned char* flags,           \
-      const T* G, double kappa, const T* kc, const T* u, const T* pold, T* pnew, T* x, T* y,      \
-      const double* scal, int beta_num, int beta_den, int xa_num, int xa_den, double* partials,   \
-      int* nblocks, hipStream_t st) {                                                             \
+  extern "C" int bdx_dofmap_apply_##SUF BDX_P_DOFMAP_APPLY(T) {                                   \
     return bdx_dofmap_apply_yz_##SUF(P, nq, geom, mode, tab, cells, ncl, nvec, cdofs, cverts,     \
                                      coords, flags, G, kappa, kc, u, pold, pnew, x, y, nullptr,   \
                                      scal, beta_num, beta_den, xa_num, xa_den, partials, nblocks, \
                                      st);                                                         \
   }                                                                                               \
-  extern "C" int bdx_dofmap_apply_yz_##SUF(                                                       \
-      int P, int nq, int geom, int mode, const T* tab, const int* cells, int ncl, int64_t nvec,   \
-      const int* cdofs, const int* cverts, const T* coords, const unsigned char* flags,           \
-      const T* G, double kappa, const T* kc, const T* u, const T* pold, T* pnew, T* x, T* y,      \
-      T* yz, const double* scal, int beta_num, int beta_den, int xa_num, int xa_den,              \
-      double* partials, int* nblocks, hipStream_t st) {                                           \
+  extern "C" int bdx_dofmap_apply_yz_##SUF BDX_P_DOFMAP_APPLY_YZ(T) {                             \
     DofArgs<T> a{cells, ncl, 0, nvec, cdofs, cverts, coords, flags, G, tab,                       \
                  static_cast<T>(kappa), kc, u, pold, pnew, x, y, scal, beta_num, beta_den,        \
                  xa_num, xa_den, partials, yz, yz ? nvec : 0};                                    \
@@ -1097,10 +1078,7 @@ int launch_dofmap_geometry(int ncells, const int* cverts, const T* coords, const
     }                                                                                             \
     return static_cast<int>(hipErrorInvalidValue);                                                \
   }                                                                                               \
-  extern "C" int bdx_dofmap_geometry_##SUF(int P, int nq, const double* phi0, const double* dphi1, \
-                                           const double* wts, const double* qpts, int ncells,     \
-                                           const int* cverts, const T* coords, T* G,              \
-                                           hipStream_t st) {                                      \
+  extern "C" int bdx_dofmap_geometry_##SUF BDX_P_DOFMAP_GEOMETRY(T) {                             \
     const OpTables<T> tb = make_op_tables<T>(P + 1, nq, phi0, dphi1, wts, qpts, 0);               \
     switch (nq) {                                                                                 \
       case 2: return launch_dofmap_geometry<T, 2>(ncells, cverts, coords, tb, G, st);             \
@@ -1114,16 +1092,11 @@ int launch_dofmap_geometry(int ncells, const int* cverts, const T* coords, const
     }                                                                                             \
     return static_cast<int>(hipErrorInvalidValue);                                                \
   }                                                                                               \
-  extern "C" int bdx_dofmap_cg_update_##SUF(int64_t n, const unsigned char* flags, T* r, T* y,    \
-                                            const double* scal, int rn_slot, int pap_slot,        \
-                                            double* partials, int* nblocks, hipStream_t st) {     \
+  extern "C" int bdx_dofmap_cg_update_##SUF BDX_P_DOFMAP_CG_UPDATE(T) {                           \
     return bdx_dofmap_cg_update_z_##SUF(n, flags, r, y, scal, rn_slot, pap_slot, partials,        \
                                         nblocks, 1, st);                                          \
   }                                                                                               \
-  extern "C" int bdx_dofmap_cg_update_z_##SUF(int64_t n, const unsigned char* flags, T* r, T* y,  \
-                                              const double* scal, int rn_slot, int pap_slot,      \
-                                              double* partials, int* nblocks, int zero_y,         \
-                                              hipStream_t st) {                                   \
+  extern "C" int bdx_dofmap_cg_update_z_##SUF BDX_P_DOFMAP_CG_UPDATE_Z(T) {                       \
     const int64_t want = (n / (16 / static_cast<int64_t>(sizeof(T))) + 256 * kDofUpdU - 1) /      \
                          (256 * kDofUpdU);                                                        \
     const int g = static_cast<int>(want < kDofMaxBlocks ? (want > 0 ? want : 1) : kDofMaxBlocks); \
@@ -1136,8 +1109,7 @@ int launch_dofmap_geometry(int ncells, const int* cverts, const T* coords, const
     *nblocks = g;                                                                                 \
     return static_cast<int>(hipGetLastError());                                                   \
   }                                                                                               \
-  extern "C" int bdx_dofmap_xflush_##SUF(int64_t n, T* x, const T* p, const double* scal,         \
-                                         int num, int den, hipStream_t st) {                      \
+  extern "C" int bdx_dofmap_xflush_##SUF BDX_P_DOFMAP_XFLUSH(T) {                                 \
     const int64_t want = (n + 1023) / 1024;                                                       \
     const int g = static_cast<int>(want < kDofMaxBlocks ? (want > 0 ? want : 1) : kDofMaxBlocks); \
     dofmap_xflush_kernel<T><<<g, 256, 0, st>>>(n, x, p, scal, num, den);                          \

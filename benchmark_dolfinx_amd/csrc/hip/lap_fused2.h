@@ -775,23 +775,28 @@ int launch_fused2(int affine, const Fused2Args<T>& a, const FusedTables<T>& tb, 
   return static_cast<int>(hipGetLastError());
 }
 
-// Workgroups of a fused2 CG instance the chip holds at once (segment sizing).
+// Workgroups of `kernel` (blocks of `threads`, no dynamic LDS) the chip holds
+// at once: the segment sizing of fused2 / fused3 / fused5.  0 if a query fails.
+template <typename K>
+int resident_workgroups(K kernel, int threads) {
+  int per_cu = 0, dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess)
+    return 0;
+  return per_cu * cus;
+}
+
+// The fused2 CG instance that sizes the segments of a launch.
 template <typename T, int ND, int NQ>
 int fused2_resident(int affine) {
   using TF = TileFor<NQ>;
   using S = FusedShape<T, ND, NQ, TF::TY, TF::TZ>;
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  const hipError_t e =
-      affine == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 1>, S::threads, 0)
-      : affine == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                          &per_cu, lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 2>, S::threads, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                          &per_cu, lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 0>, S::threads, 0);
-  return e == hipSuccess ? per_cu * cus : 0;
+  return resident_workgroups(
+      affine == 1   ? lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 1>
+      : affine == 2 ? lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 2>
+                    : lap_fused2_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 0>,
+      S::threads);
 }
 
 template <typename T>
@@ -920,37 +925,49 @@ inline int fused_set_segments(Fused2Args<T>& a, int nseg) {
   return 0;
 }
 
+// Host-side launch prologue of the fused2 / fused3 / fused5 apply entry points
+// (BDX_P_FUSED_APPLY, bdx_hip_api.h): the argument block from the lattice
+// descriptor, the tile rectangle, the x segments (mode bits 8-15) and the entry
+// point's vectors, scalar slots and kappa.  What differs between the three
+// (tiled storage, x-mode bits, tables) stays at their call sites.
+template <typename T>
+int fill_fused2_args(Fused2Args<T>& a, int mode, const int64_t* latd, int nty, int ntz,
+                     const int* rect, const T* u, const T* pold, T* pnew, T* x, T* y, T* yb, T* zb,
+                     T* cb, const T* xv, const T* kc, double kappa, const double* scal,
+                     double* partials, int beta_num, int beta_den, int xa_num, int xa_den) {
+  BDX_CHECK(static_cast<hipError_t>(make_fused2_args(a, latd, nty, ntz)));
+  BDX_CHECK(static_cast<hipError_t>(fused_set_rect(a, rect)));
+  BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, (mode >> 8) & 0xff)));
+  a.u = u;
+  a.pold = pold;
+  a.pnew = pnew;
+  a.x = x;
+  a.y = y;
+  a.yb = yb;
+  a.zb = zb;
+  a.cb = cb;
+  a.xv = xv;
+  a.kc = kc;
+  a.scal = scal;
+  a.partials = partials;
+  a.beta_num = beta_num;
+  a.beta_den = beta_den;
+  a.xa_num = xa_num;
+  a.xa_den = xa_den;
+  a.kappa = static_cast<T>(kappa);
+  return 0;
+}
+// The prologue's arguments, by the parameter names of BDX_P_FUSED_APPLY.
+#define BDX_FUSED_FILL_ARGS                                                              \
+  a, mode, latd, nty, ntz, rect, u, pold, pnew, x, y, yb, zb, cb, xv, kc, kappa, scal,   \
+      partials, beta_num, beta_den, xa_num, xa_den
+
 #define BDX_FUSED2_TU(T, SUF, PP)                                                   \
-  extern "C" int bdx_fused2_apply_##SUF##_p##PP(                                   \
-      int mode, int affine_ok, const int64_t* latd, int nq, const double* wts,     \
-      const double* qpts,                                                          \
-      const T* u, const T* pold, T* pnew, T* x, T* y, T* yb, T* zb, T* cb,         \
-      const T* xv, const T* kc, const T* tabs, double kappa, const double* scal,   \
-      double* partials, int beta_num, int beta_den, int xa_num, int xa_den,        \
-      int nty, int ntz, const int* rect, hipStream_t st) {                                          \
+  extern "C" int bdx_fused2_apply_##SUF##_p##PP BDX_P_FUSED_APPLY(T) {             \
     Fused2Args<T> a;                                                               \
-    BDX_CHECK(static_cast<hipError_t>(make_fused2_args(a, latd, nty, ntz)));  \
+    BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
     if (a.tsy) return static_cast<int>(hipErrorInvalidValue); /* lattice layout only */ \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_rect(a, rect)));       \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, (mode >> 8) & 0xff))); \
     mode &= 0xff;                                                                  \
-    a.u = u;                                                                       \
-    a.pold = pold;                                                                 \
-    a.pnew = pnew;                                                                 \
-    a.x = x;                                                                       \
-    a.y = y;                                                                       \
-    a.yb = yb;                                                                     \
-    a.zb = zb;                                                                     \
-    a.cb = cb;                                                                     \
-    a.xv = xv;                                                                     \
-    a.kc = kc;                                                                     \
-    a.scal = scal;                                                                 \
-    a.partials = partials;                                                         \
-    a.beta_num = beta_num;                                                         \
-    a.beta_den = beta_den;                                                         \
-    a.xa_num = xa_num;                                                             \
-    a.xa_den = xa_den;                                                             \
-    a.kappa = static_cast<T>(kappa);                                               \
     if (!tabs) return static_cast<int>(hipErrorInvalidValue);                      \
     FusedTables<T> tb;                                                             \
     for (int i = 0; i < kFusedTabMax; ++i) tb.tab[i] = tabs[i];                    \

@@ -1323,57 +1323,24 @@ int launch_fused3(int affine, const Fused2Args<T>& a, const FusedTables<T>& tb, 
   return static_cast<int>(hipGetLastError());
 }
 
-// Workgroups of a fused3 CG instance the chip holds at once (segment sizing).
+// The fused3 CG instance that sizes the segments of a launch.
 template <typename T, int ND, int NQ>
 int fused3_resident(int affine) {
   using TF = TileFor<NQ>;
   using S = FusedShape<T, ND, NQ, TF::TY, TF::TZ>;
-  int per_cu = 0, dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return 0;
-  const hipError_t e =
-      affine == 1 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                        &per_cu, lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 1>, S::threads, 0)
-      : affine == 2 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                          &per_cu, lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 2,
-                                                     f3_vec_shape<T, ND, NQ>()>, S::threads, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                          &per_cu, lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 0,
-                                                     f3_vec_shape<T, ND, NQ>()>, S::threads, 0);
-  return e == hipSuccess ? per_cu * cus : 0;
+  constexpr bool VEC = f3_vec_shape<T, ND, NQ>();
+  return resident_workgroups(
+      affine == 1   ? lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 1>
+      : affine == 2 ? lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 2, VEC>
+                    : lap_fused3_kernel<T, ND, NQ, TF::TY, TF::TZ, kFusedCG, 0, VEC>,
+      S::threads);
 }
 
 #define BDX_FUSED3_TU(T, SUF, PP)                                                   \
-  extern "C" int bdx_fused3_apply_##SUF##_p##PP(                                   \
-      int mode, int affine_ok, const int64_t* latd, int nq, const double* wts,     \
-      const double* qpts,                                                          \
-      const T* u, const T* pold, T* pnew, T* x, T* y, T* yb, T* zb, T* cb,         \
-      const T* xv, const T* kc, const T* tabs, double kappa, const double* scal,   \
-      double* partials, int beta_num, int beta_den, int xa_num, int xa_den,        \
-      int nty, int ntz, const int* rect, hipStream_t st) {                                          \
+  extern "C" int bdx_fused3_apply_##SUF##_p##PP BDX_P_FUSED_APPLY(T) {             \
     Fused2Args<T> a;                                                               \
-    BDX_CHECK(static_cast<hipError_t>(make_fused2_args(a, latd, nty, ntz)));  \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_rect(a, rect)));       \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, (mode >> 8) & 0xff))); \
+    BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
     mode &= 0xff;                                                                  \
-    a.u = u;                                                                       \
-    a.pold = pold;                                                                 \
-    a.pnew = pnew;                                                                 \
-    a.x = x;                                                                       \
-    a.y = y;                                                                       \
-    a.yb = yb;                                                                     \
-    a.zb = zb;                                                                     \
-    a.cb = cb;                                                                     \
-    a.xv = xv;                                                                     \
-    a.kc = kc;                                                                     \
-    a.scal = scal;                                                                 \
-    a.partials = partials;                                                         \
-    a.beta_num = beta_num;                                                         \
-    a.beta_den = beta_den;                                                         \
-    a.xa_num = xa_num;                                                             \
-    a.xa_den = xa_den;                                                             \
-    a.kappa = static_cast<T>(kappa);                                               \
     if (!tabs) return static_cast<int>(hipErrorInvalidValue);                      \
     FusedTables<T> tb;                                                             \
     for (int i = 0; i < kFusedTabMax; ++i) tb.tab[i] = tabs[i];                    \

@@ -1039,42 +1039,18 @@ int launch_fused5(int affine_ok, const Fused2Args<T>& a, const T* tabd, hipStrea
 }
 
 #define BDX_FUSED5_TU(T, SUF, PP)                                                   \
-  extern "C" int bdx_fused5_apply_##SUF##_p##PP(                                   \
-      int mode, int affine_ok, const int64_t* latd, int nq, const double* wts,     \
-      const double* qpts, const T* u, const T* pold, T* pnew, T* x, T* y, T* yb,   \
-      T* zb, T* cb, const T* xv, const T* kc, const T* tabs, double kappa,         \
-      const double* scal, double* partials, int beta_num, int beta_den,            \
-      int xa_num, int xa_den, int nty, int ntz, const int* rect, hipStream_t st) {                  \
+  extern "C" int bdx_fused5_apply_##SUF##_p##PP BDX_P_FUSED_APPLY(T) {             \
     (void)wts;                                                                     \
     (void)qpts;                                                                    \
     (void)nq;                                                                      \
     if (!affine_ok || !tabs) return static_cast<int>(hipErrorInvalidValue);        \
     Fused2Args<T> a;                                                               \
-    BDX_CHECK(static_cast<hipError_t>(make_fused2_args(a, latd, nty, ntz)));  \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_rect(a, rect)));       \
-    BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, (mode >> 8) & 0xff))); \
+    BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
     a.xmode = (mode >> 4) & 3;                                                     \
     a.xmode1 = ((mode >> 6) & 3) - 1;                                              \
     a.xslot_w = kScalXSave + ((mode >> 16) & 1);                                   \
     a.xslot_r = kScalXSave + ((mode >> 17) & 1);                                   \
     mode &= 0xf;                                                                   \
-    a.u = u;                                                                       \
-    a.pold = pold;                                                                 \
-    a.pnew = pnew;                                                                 \
-    a.x = x;                                                                       \
-    a.y = y;                                                                       \
-    a.yb = yb;                                                                     \
-    a.zb = zb;                                                                     \
-    a.cb = cb;                                                                     \
-    a.xv = xv;                                                                     \
-    a.kc = kc;                                                                     \
-    a.scal = scal;                                                                 \
-    a.partials = partials;                                                         \
-    a.beta_num = beta_num;                                                         \
-    a.beta_den = beta_den;                                                         \
-    a.xa_num = xa_num;                                                             \
-    a.xa_den = xa_den;                                                             \
-    a.kappa = static_cast<T>(kappa);                                               \
     const T* tabd = tabs; /* device pointer: the operator's own table buffer */   \
     return mode == kFusedCG ? launch_fused5<T, PP + 1, kFusedCG>(affine_ok, a, tabd, st) \
                             : launch_fused5<T, PP + 1, kFusedAction>(affine_ok, a, tabd, st); \
@@ -1085,16 +1061,11 @@ int launch_fused5(int affine_ok, const Fused2Args<T>& a, const T* tabd, hipStrea
     return pack_tables5<T>(nd, nq, phi0, Dd, wts, out);                            \
   }                                                                                \
   extern "C" int bdx_fused5_segments_##SUF##_p##PP(int affine_ok, int tiles, int ncx) { \
-    int per_cu = 0, dev = 0, cus = 0;                                              \
-    hipError_t e = hipGetDevice(&dev);                                             \
-    if (e == hipSuccess)                                                           \
-      e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); \
     if (affine_ok != 2) return 1;                                                  \
-    if (e == hipSuccess)                                                           \
-      e = hipOccupancyMaxActiveBlocksPerMultiprocessor(                            \
-          &per_cu, lap_fused5_kernel<T, PP + 1, kFusedCG, f5_vec_shape<T, PP + 1>()>, \
-          F5Shape<T, PP + 1>::NT, 0);                                              \
-    return e == hipSuccess ? fused_choose_segments(tiles, ncx, per_cu * cus) : 1;  \
+    return fused_choose_segments(                                                  \
+        tiles, ncx,                                                                \
+        resident_workgroups(lap_fused5_kernel<T, PP + 1, kFusedCG, f5_vec_shape<T, PP + 1>()>, \
+                            F5Shape<T, PP + 1>::NT));                              \
   }                                                                                \
   extern "C" int bdx_fused5_tile_p##PP##_##SUF(int affine_ok, int* ty, int* tz) {  \
     (void)affine_ok;                                                               \

@@ -26,15 +26,9 @@ int launch_fused_any(int geom, int mode, const FusedArgs<T>& a, const FusedTable
                           : launch_fused<T, ND, NQ, kGeomStored, kFusedAction>(a, tb, st);
 }
 
-// Per-(T, P) entry point: nq in {P+1, P+2}.
-#define BDX_FUSED_TU(T, SUF, PP)                                                   \
-  extern "C" int bdx_fused_apply_##SUF##_p##PP(                                   \
-      int geom, int mode, const int64_t* latd, int nq, const double* phi0,        \
-      const double* dphi1, const double* wts, const double* qpts, const T* u,     \
-      const T* pold, T* pnew, T* y, T* yb, T* zb, T* cb, const T* G, const T* xv, \
-      const T* tabs /* host, kFusedTabMax values */,                              \
-      double kappa, const double* scal, double* partials, int beta_num,           \
-      int beta_den, int nty, int ntz, hipStream_t st) {                            \
+// Per-(T, P) entry point (bdx_hip_api.h).
+#define BDX_FUSED_TU(T, SUF, PP)                                                  \
+  extern "C" int bdx_fused_apply_##SUF##_p##PP BDX_P_FUSED_V1_APPLY(T) {          \
     FusedArgs<T> a;                                                               \
     a.lat = BdxLattice::from(latd);                                               \
     a.u = u;                                                                      \

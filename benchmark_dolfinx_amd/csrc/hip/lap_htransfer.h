@@ -117,18 +117,10 @@ int launch_hrestrict(const int64_t* latc, const int64_t* latf, const int* cidx, 
   return 0;
 }
 
-// vf (+)= P vc and vc = P^T (vf - y) between the coarse and fine degree-1
-// lattices latc / latf; cidx, cw, fpos: the device tables above.
-// hipErrorInvalidValue for tiled descriptors, a degree other than 1, differing
-// ghost flags, L != n + 1, more coarse than fine cells on an axis or ld < L[2].
 #define BDX_HTRANSFER_API(T, SUF)                                                              \
-  extern "C" int bdx_hprolong_##SUF(const int64_t* latc, const int64_t* latf, const int* cidx, \
-                                    const T* cw, const int* fpos, const T* vc, T* vf, int add, \
-                                    hipStream_t st) {                                          \
+  extern "C" int bdx_hprolong_##SUF BDX_P_HPROLONG(T) {                                        \
     return launch_hprolong<T>(latc, latf, cidx, cw, fpos, vc, vf, add, st);                    \
   }                                                                                            \
-  extern "C" int bdx_hrestrict_##SUF(const int64_t* latc, const int64_t* latf, const int* cidx, \
-                                     const T* cw, const int* fpos, const T* vf, const T* y,    \
-                                     T* vc, hipStream_t st) {                                  \
+  extern "C" int bdx_hrestrict_##SUF BDX_P_HRESTRICT(T) {                                      \
     return launch_hrestrict<T>(latc, latf, cidx, cw, fpos, vf, y, vc, st);                     \
   }

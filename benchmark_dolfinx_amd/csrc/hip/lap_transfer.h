@@ -240,17 +240,12 @@ int dispatch_transfer(bool restrict_, const BdxLattice& lc, const BdxLattice& lf
   return static_cast<int>(hipErrorInvalidValue);
 }
 
-// vf = P vc (every local fine node, ghost planes included, written once) and
-// vc += P^T vf (owned fine nodes; vc zeroed by the caller).  latc / latf: the
-// coarse and fine lattice descriptors, J: the (Pf + 1) x (Pc + 1) 1D table.
 #define BDX_TRANSFER_API(T, SUF)                                                          \
-  extern "C" int bdx_prolong_##SUF(const int64_t* latc, const int64_t* latf, const double* J, \
-                                   const T* vc, T* vf, hipStream_t st) {                  \
+  extern "C" int bdx_prolong_##SUF BDX_P_PROLONG(T) {                                     \
     return dispatch_transfer<T>(false, BdxLattice::from(latc), BdxLattice::from(latf), J, \
                                 vc, vf, st);                                              \
   }                                                                                       \
-  extern "C" int bdx_restrict_##SUF(const int64_t* latc, const int64_t* latf, const double* J, \
-                                    const T* vf, T* vc, hipStream_t st) {                 \
+  extern "C" int bdx_restrict_##SUF BDX_P_RESTRICT(T) {                                   \
     return dispatch_transfer<T>(true, BdxLattice::from(latc), BdxLattice::from(latf), J,  \
                                 vf, vc, st);                                              \
   }

@@ -45,14 +45,8 @@ int dispatch_v1(int P, int nq, const BdxLattice& lat, const OpTables<T>& tb,
   return static_cast<int>(hipErrorInvalidValue);
 }
 
-// mode: 0 stiffness (stored G), 1 stiffness (on-the-fly geometry), 2 mass
 #define BDX_V1_API(T, SUF)                                                     \
-  extern "C" int bdx_v1_apply_##SUF(                                           \
-      int mode, const int64_t* latd, int nq, const double* phi0,               \
-      const double* dphi1, const double* wts, const double* qpts,              \
-      int identity, const T* G, const T* xv, double kappa, const T* kc,        \
-      const T* u, T* y,                                                        \
-      const int64_t* lo, const int64_t* hi, hipStream_t st) {                  \
+  extern "C" int bdx_v1_apply_##SUF BDX_P_V1_APPLY(T) {                        \
     const BdxLattice lat = BdxLattice::from(latd);                             \
     const int P = static_cast<int>(lat.P);                                     \
     const OpTables<T> tb =                                                     \

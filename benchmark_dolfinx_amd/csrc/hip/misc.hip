@@ -96,18 +96,13 @@ __global__ void __launch_bounds__(256)
 extern "C" {
 
 #define BDX_MISC_API(T, SUF)                                                  \
-  int bdx_geometry_##SUF(const int64_t* latd, int nq, const double* phi0,     \
-                         const double* dphi1, const double* wts,              \
-                         const double* qpts, const T* xv, T* G,               \
-                         hipStream_t st) {                                    \
+  int bdx_geometry_##SUF BDX_P_GEOMETRY(T) {                                  \
     const BdxLattice lat = BdxLattice::from(latd);                            \
     const OpTables<T> tb = make_op_tables<T>(static_cast<int>(lat.P) + 1, nq, \
                                              phi0, dphi1, wts, qpts, 0);      \
     return launch_geometry<T>(nq, lat, tb, xv, G, st);                        \
   }                                                                           \
-  int bdx_spmv_##SUF(int64_t nrows, const int64_t* beg, const int64_t* end,    \
-                     const int32_t* cols, const T* vals, const T* x, T* y,    \
-                     int acc, hipStream_t st) {                               \
+  int bdx_spmv_##SUF BDX_P_SPMV(T) {                                          \
     if (nrows <= 0) return 0;                                                 \
     spmv_kernel<T><<<static_cast<unsigned>((nrows + 3) / 4), 256, 0, st>>>(   \
         nrows, beg, end, cols, vals, x, y, acc);                              \

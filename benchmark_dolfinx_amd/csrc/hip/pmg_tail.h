@@ -169,11 +169,7 @@ int launch_pmg_tail(const int64_t* htab, const int64_t* dtab, int nlev, int64_t 
   return 0;
 }
 
-// z = the V-cycle from the first level of the table down and back up, applied
-// to r (the table's other vectors are work space); htab / dtab: the host and
-// device copies of the level table, nwords long.
 #define BDX_PMG_TAIL_API(T, SUF)                                                                 \
-  extern "C" int bdx_pmg_tail_##SUF(const int64_t* htab, const int64_t* dtab, int nlev,          \
-                                    int64_t nwords, const T* r, T* z, hipStream_t st) {          \
+  extern "C" int bdx_pmg_tail_##SUF BDX_P_PMG_TAIL(T) {                                          \
     return launch_pmg_tail<T>(htab, dtab, nlev, nwords, r, z, st);                               \
   }

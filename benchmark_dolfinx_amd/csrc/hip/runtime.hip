@@ -36,464 +36,57 @@
 //
 // Python (solvers/native.py) builds the problem, runs the CG prologue
 // (r0 = b - A x0, rho0) and hands the device buffers to this runtime.
-#include <rccl/rccl.h>
-
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <type_traits>
 #include <vector>
 
-#include "bdx_common.h"
-#include "bdx_watchdog.h"
+#include "rt_transport.h"  // Transport and its four implementations, bdx_common.h
 
-extern "C" {
-int bdx_box_copy_f64(int, double*, int64_t, int64_t, const int64_t*, int, int64_t, double*,
-                     hipStream_t);
-int bdx_box_copy_f32(int, float*, int64_t, int64_t, const int64_t*, int, int64_t, float*,
-                     hipStream_t);
-int bdx_reduce_partials(const double*, int, double*, int, hipStream_t);
-int bdx_fused_finalize_f64(const int64_t*, double*, const double*, const double*,
-                           const double*, int, int, int, int, int, hipStream_t);
-int bdx_fused_finalize_f32(const int64_t*, float*, const float*, const float*, const float*,
-                           int, int, int, int, int, hipStream_t);
-int bdx_cg_update_iface_f64(const int64_t*, const int64_t*, double*, const double*,
-                            const double*, const double*, const double*, int, int, int, int,
-                            double*, int, int, int, double*, hipStream_t);
-int bdx_cg_update_iface_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
-                            const float*, const float*, int, int, int, int, double*, int, int,
-                            int, double*, hipStream_t);
-int bdx_xflush_f64(const int64_t*, const int64_t*, double*, const double*, const double*, int,
-                   int, hipStream_t);
-int bdx_xflush_f32(const int64_t*, const int64_t*, float*, const float*, const double*, int,
-                   int, hipStream_t);
-int bdx_box_copy_lat_f64(int, double*, const int64_t*, const int64_t*, int, int64_t, double*,
-                         hipStream_t);
-int bdx_box_copy_lat_f32(int, float*, const int64_t*, const int64_t*, int, int64_t, float*,
-                         hipStream_t);
-int bdx_layout_convert_f64(int, const int64_t*, double*, double*, hipStream_t);
-int bdx_layout_convert_f32(int, const int64_t*, float*, float*, hipStream_t);
-int bdx_flush_export_f64(const int64_t*, double*, double*, const double*, const double*,
-                         const double*, int, int, int, int, int, hipStream_t);
-int bdx_flush_export_f32(const int64_t*, float*, float*, const float*, const float*,
-                         const double*, int, int, int, int, int, hipStream_t);
-int bdx_cg_update_tiled_f64(const int64_t*, const int64_t*, double*, const double*, const double*,
-                            const double*, const double*, int, int, double*, int, int, int,
-                            double*, hipStream_t);
-int bdx_cg_update_tiled_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
-                            const float*, const float*, int, int, double*, int, int, int, double*,
-                            hipStream_t);
-int bdx_pcg_update_iface_f64(const int64_t*, const int64_t*, double*, const double*,
-                             const double*, const double*, const double*, int, int, int, int,
-                             double*, int, int, int, double*, const double*, double*, int, double*,
-                             hipStream_t);
-int bdx_pcg_update_iface_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
-                             const float*, const float*, int, int, int, int, double*, int, int,
-                             int, double*, const float*, float*, int, double*, hipStream_t);
-int bdx_pcg_update_tiled_f64(const int64_t*, const int64_t*, double*, const double*,
-                             const double*, const double*, const double*, int, int, double*, int,
-                             int, int, double*, const double*, double*, int, double*, hipStream_t);
-int bdx_pcg_update_tiled_f32(const int64_t*, const int64_t*, float*, const float*, const float*,
-                             const float*, const float*, int, int, double*, int, int, int, double*,
-                             const float*, float*, int, double*, hipStream_t);
-}
-
-// The fused2, fused3 and fused5 operator entry points (lap_fused{2,3,5}_<suf>_p<P>.hip);
-// weak so that experiment builds holding a subset of the operator TUs still
-// load (a missing instance resolves to null and bdx_rt_create refuses it).
-#define BDX_DECL_APPLY(V, T, SUF, PP)                                                        \
-  extern "C" __attribute__((weak)) int bdx_fused##V##_apply_##SUF##_p##PP(                  \
-      int, int, const int64_t*, int, const double*, const double*, const T*, const T*, T*, \
-      T*, T*, T*, T*, T*, const T*, const T*, const T*, double, const double*, double*, int, \
-      int, int, int, int, int, const int*, hipStream_t);
-#define BDX_DECL_ALL(V)                                                                    \
-  BDX_DECL_APPLY(V, double, f64, 1) BDX_DECL_APPLY(V, double, f64, 2)                      \
-  BDX_DECL_APPLY(V, double, f64, 3) BDX_DECL_APPLY(V, double, f64, 4)                      \
-  BDX_DECL_APPLY(V, double, f64, 5) BDX_DECL_APPLY(V, double, f64, 6)                      \
-  BDX_DECL_APPLY(V, double, f64, 7) BDX_DECL_APPLY(V, float, f32, 1)                       \
-  BDX_DECL_APPLY(V, float, f32, 2) BDX_DECL_APPLY(V, float, f32, 3)                        \
-  BDX_DECL_APPLY(V, float, f32, 4) BDX_DECL_APPLY(V, float, f32, 5)                        \
-  BDX_DECL_APPLY(V, float, f32, 6) BDX_DECL_APPLY(V, float, f32, 7)
-BDX_DECL_ALL(2)
-BDX_DECL_ALL(3)
-#define BDX_DECL_F5(T, SUF) \
-  BDX_DECL_APPLY(5, T, SUF, 3) BDX_DECL_APPLY(5, T, SUF, 4) BDX_DECL_APPLY(5, T, SUF, 5) \
-  BDX_DECL_APPLY(5, T, SUF, 6) BDX_DECL_APPLY(5, T, SUF, 7)
-BDX_DECL_F5(double, f64)
-BDX_DECL_F5(float, f32)
-
-// The dofmap data model's entry points (lap_dofmap.h, lap_dofmap_f{32,64}.hip).
-#define BDX_DECL_DOF(T, SUF)                                                                  \
-  extern "C" int bdx_dofmap_apply_##SUF(                                                      \
-      int, int, int, int, const T*, const int*, int, int64_t, const int*, const int*, const T*, \
-      const unsigned char*, const T*, double, const T*, const T*, const T*, T*, T*, T*,        \
-      const double*, int, int, int, int, double*, int*, hipStream_t);                          \
-  extern "C" int bdx_dofmap_cg_update_##SUF(int64_t, const unsigned char*, T*, T*,              \
-                                            const double*, int, int, double*, int*, hipStream_t); \
-  extern "C" int bdx_dofmap_apply_yz_##SUF(                                                   \
-      int, int, int, int, const T*, const int*, int, int64_t, const int*, const int*, const T*, \
-      const unsigned char*, const T*, double, const T*, const T*, const T*, T*, T*, T*, T*,    \
-      const double*, int, int, int, int, double*, int*, hipStream_t);                          \
-  extern "C" int bdx_dofmap_cg_update_z_##SUF(int64_t, const unsigned char*, T*, T*,            \
-                                              const double*, int, int, double*, int*, int,      \
-                                              hipStream_t);                                     \
-  extern "C" int bdx_dofmap_xflush_##SUF(int64_t, T*, const T*, const double*, int, int,        \
-                                         hipStream_t);
-BDX_DECL_DOF(double, f64)
-BDX_DECL_DOF(float, f32)
-// p.Ap partials of a dofmap launch (lap_dofmap_f64.hip)
-extern "C" int bdx_dofmap_nblocks(int nq, int ncl);
-// capacity of the partials buffers (blas.hip)
-extern "C" int bdx_hip_partials_size();
+// The fused2, fused3 and fused5 operator entry points (lap_fused{2,3,5}_<suf>_p<P>.hip)
+// are referenced weakly, here alone, so that experiment builds holding a
+// subset of the operator TUs still load (a missing instance resolves to null
+// and bdx_rt_create refuses it).
+#define BDX_PRAGMA(x) _Pragma(#x)
+#define BDX_WEAK_APPLY(PP, V, SUF) BDX_PRAGMA(weak bdx_fused##V##_apply_##SUF##_p##PP)
+BDX_FUSED_DEGREES(BDX_WEAK_APPLY, 2, f64)
+BDX_FUSED_DEGREES(BDX_WEAK_APPLY, 2, f32)
+BDX_FUSED_DEGREES(BDX_WEAK_APPLY, 3, f64)
+BDX_FUSED_DEGREES(BDX_WEAK_APPLY, 3, f32)
+BDX_FUSED5_DEGREES(BDX_WEAK_APPLY, 5, f64)
+BDX_FUSED5_DEGREES(BDX_WEAK_APPLY, 5, f32)
 
 namespace {
 
-template <typename T>
-using ApplyFn = int (*)(int, int, const int64_t*, int, const double*, const double*, const T*,
-                        const T*, T*, T*, T*, T*, T*, T*, const T*, const T*, const T*, double,
-                        const double*, double*, int, int, int, int, int, int, const int*,
-                        hipStream_t);
+// The _f64 / _f32 twin of an entry point for the scalar type T, chosen at
+// compile time: BDX_TWIN(T, bdx_xflush)(args...) is a direct call.
+template <typename T, typename F64, typename F32>
+constexpr auto twin(F64* f64, F32* f32) {
+  if constexpr (sizeof(T) == 8)
+    return f64;
+  else
+    return f32;
+}
+#define BDX_TWIN(T, NAME) twin<T>(NAME##_f64, NAME##_f32)
 
 template <typename T>
-ApplyFn<T> apply_fn(int version, int P);
-template <>
-ApplyFn<double> apply_fn<double>(int version, int P) {
-#define BDX_CASE(V, PP) \
-  if (version == V && P == PP) return bdx_fused##V##_apply_f64_p##PP;
-  BDX_CASE(2, 1) BDX_CASE(2, 2) BDX_CASE(2, 3) BDX_CASE(2, 4) BDX_CASE(2, 5) BDX_CASE(2, 6)
-  BDX_CASE(2, 7) BDX_CASE(3, 1) BDX_CASE(3, 2) BDX_CASE(3, 3) BDX_CASE(3, 4) BDX_CASE(3, 5)
-  BDX_CASE(3, 6) BDX_CASE(3, 7) BDX_CASE(5, 3) BDX_CASE(5, 4) BDX_CASE(5, 5) BDX_CASE(5, 6)
-  BDX_CASE(5, 7)
+using ApplyFn = int(*) BDX_P_FUSED_APPLY(T);
+
+// The fused operator instance of (version, degree); null if the build lacks it.
+template <typename T>
+ApplyFn<T> apply_fn(int version, int P) {
+#define BDX_CASE(PP, V)         \
+  if (version == V && P == PP) \
+    return twin<T>(bdx_fused##V##_apply_f64_p##PP, bdx_fused##V##_apply_f32_p##PP);
+  BDX_FUSED_DEGREES(BDX_CASE, 2)
+  BDX_FUSED_DEGREES(BDX_CASE, 3)
+  BDX_FUSED5_DEGREES(BDX_CASE, 5)
 #undef BDX_CASE
   return nullptr;
 }
-template <>
-ApplyFn<float> apply_fn<float>(int version, int P) {
-#define BDX_CASE(V, PP) \
-  if (version == V && P == PP) return bdx_fused##V##_apply_f32_p##PP;
-  BDX_CASE(2, 1) BDX_CASE(2, 2) BDX_CASE(2, 3) BDX_CASE(2, 4) BDX_CASE(2, 5) BDX_CASE(2, 6)
-  BDX_CASE(2, 7) BDX_CASE(3, 1) BDX_CASE(3, 2) BDX_CASE(3, 3) BDX_CASE(3, 4) BDX_CASE(3, 5)
-  BDX_CASE(3, 6) BDX_CASE(3, 7) BDX_CASE(5, 3) BDX_CASE(5, 4) BDX_CASE(5, 5) BDX_CASE(5, 6)
-  BDX_CASE(5, 7)
-#undef BDX_CASE
-  return nullptr;
-}
-
-// Error codes returned to Python (besides hipError_t values).
-constexpr int kErrAborted = -20;   // the watchdog aborted the communicator
-constexpr int kErrNotConnected = -21;
-
-// ------------------------------------------------------------------ transports
-struct Transport {
-  virtual ~Transport() = default;
-  // Grouped point-to-point exchange: rank p receives rcnt[p] elements from
-  // each peer (into rbuf + roff[p]) and sends scnt[p] elements to it.
-  virtual int exchange(const void* sbuf, const std::vector<int64_t>& scnt,
-                       const std::vector<int64_t>& soff, void* rbuf,
-                       const std::vector<int64_t>& rcnt, const std::vector<int64_t>& roff,
-                       int esize, hipStream_t st) = 0;
-  virtual int allreduce_sum(double* dev, int n, hipStream_t st) = 0;
-  virtual bool capturable() const = 0;
-  virtual int ranks() const = 0;
-  // Host wait for `ev` (the end of queued work that may contain
-  // communication), bounded by the transport's deadline.
-  virtual int wait(hipEvent_t ev) { return static_cast<int>(hipEventSynchronize(ev)); }
-  virtual bool aborted() const { return false; }
-  // Deadline watchdog whose Busy scopes must cover every host call that can
-  // block behind a stuck peer (RCCL only; null otherwise).
-  virtual bdx::Watchdog* watchdog() { return nullptr; }
-};
-
-double rccl_timeout_s() {
-  const char* e = std::getenv("BDX_RCCL_TIMEOUT_S");
-  return e ? std::atof(e) : 300.0;
-}
-
-struct RcclTransport final : Transport {
-  std::atomic<ncclComm_t> comm{nullptr};
-  int nranks = 1;
-  std::atomic<bool> was_aborted{false};
-  std::unique_ptr<bdx::Watchdog> wd;
-
-  RcclTransport() {
-    wd = std::make_unique<bdx::Watchdog>(
-        rccl_timeout_s(),
-        [this] {
-          ncclComm_t c = comm.load();
-          if (!c || was_aborted.load()) return false;
-          ncclResult_t e = ncclSuccess;
-          if (ncclCommGetAsyncError(c, &e) != ncclSuccess) return true;
-          return e != ncclSuccess && e != ncclInProgress;
-        },
-        [this] {
-          ncclComm_t c = comm.load();
-          if (!c) {
-            // still inside ncclCommInitRank: nothing to abort, fail fast
-            std::fprintf(stderr,
-                         "[bdx] RCCL communicator init exceeded %.0f s; a peer never joined. "
-                         "Exiting.\n",
-                         wd->timeout_s());
-            std::fflush(stderr);
-            std::_Exit(124);
-          }
-          std::fprintf(stderr, "[bdx] RCCL %s; aborting the communicator\n",
-                       wd->reason() == 1 ? "call exceeded the deadline" : "asynchronous error");
-          std::fflush(stderr);
-          was_aborted.store(true);
-          ncclCommAbort(c);
-        });
-  }
-  ~RcclTransport() override {
-    if (wd) wd->stop();
-    ncclComm_t c = comm.load();
-    if (c && !was_aborted.load()) ncclCommDestroy(c);
-  }
-  int connect(const ncclUniqueId& id, int n, int rank) {
-    nranks = n;
-    wd->start();
-    bdx::Watchdog::Busy b(wd.get());
-    ncclComm_t c = nullptr;
-    if (ncclCommInitRank(&c, n, id, rank) != ncclSuccess) return -1;
-    comm.store(c);
-    return 0;
-  }
-  bool aborted() const override { return was_aborted.load(); }
-  bdx::Watchdog* watchdog() override { return wd.get(); }
-  int exchange(const void* sbuf, const std::vector<int64_t>& scnt,
-               const std::vector<int64_t>& soff, void* rbuf, const std::vector<int64_t>& rcnt,
-               const std::vector<int64_t>& roff, int esize, hipStream_t st) override {
-    ncclComm_t c = comm.load();
-    if (!c) return kErrNotConnected;
-    if (was_aborted.load()) return kErrAborted;
-    bdx::Watchdog::Busy b(wd.get());
-    const ncclDataType_t dt = esize == 8 ? ncclFloat64 : ncclFloat32;
-    if (ncclGroupStart() != ncclSuccess) return -1;
-    for (int p = 0; p < nranks; ++p) {
-      if (scnt[p] > 0 &&
-          ncclSend(static_cast<const char*>(sbuf) + soff[p] * esize, scnt[p], dt, p, c, st) !=
-              ncclSuccess)
-        return -2;
-      if (rcnt[p] > 0 &&
-          ncclRecv(static_cast<char*>(rbuf) + roff[p] * esize, rcnt[p], dt, p, c, st) !=
-              ncclSuccess)
-        return -3;
-    }
-    const ncclResult_t e = ncclGroupEnd();
-    if (was_aborted.load()) return kErrAborted;
-    return e == ncclSuccess ? 0 : -4;
-  }
-  int allreduce_sum(double* dev, int n, hipStream_t st) override {
-    ncclComm_t c = comm.load();
-    if (!c) return kErrNotConnected;
-    if (was_aborted.load()) return kErrAborted;
-    bdx::Watchdog::Busy b(wd.get());
-    const ncclResult_t e = ncclAllReduce(dev, dev, n, ncclFloat64, ncclSum, c, st);
-    if (was_aborted.load()) return kErrAborted;
-    return e == ncclSuccess ? 0 : -5;
-  }
-  int wait(hipEvent_t ev) override {
-    bdx::Watchdog::Busy b(wd.get());
-    for (;;) {
-      const hipError_t e = hipEventQuery(ev);
-      if (e == hipSuccess) return 0;
-      if (e != hipErrorNotReady) return static_cast<int>(e);
-      if (was_aborted.load()) return kErrAborted;
-      std::this_thread::sleep_for(std::chrono::microseconds(200));
-    }
-  }
-  bool capturable() const override { return true; }
-  int ranks() const override {
-    ncclComm_t c = comm.load();
-    int n = 0;
-    if (!c || ncclCommCount(c, &n) != ncclSuccess) return -1;
-    return n;
-  }
-};
-
-// Emulated link (one rank of an N-rank run alone on this device: bench /
-// scripts/emulate_rank.py).  Every exchange is a device copy of the send
-// buffer into the receive buffer by a few workgroups (RCCL's p2p kernels
-// occupy a few CUs the same way) that hold their CUs until the modelled link
-// time has passed: max over peers of the bytes to or from that peer /
-// link_gbps (one xGMI link per peer) + lat_us.  An all-reduce is a single
-// workgroup held for allreduce_us.  The copies carry the rank's own face
-// data, not a peer's: the emulation is for timing the schedule, not for
-// results.  Bounded: each workgroup waits on the 100 MHz constant clock from
-// its own start, nothing else.
-__global__ void __launch_bounds__(256)
-    bdx_link_emu_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int64_t n16,
-                        int64_t ticks) {
-  const long long t0 = wall_clock64();
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n16;
-       i += static_cast<int64_t>(gridDim.x) * 256)
-    dst[i] = src[i];
-  if (threadIdx.x == 0) {
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-  }
-  __syncthreads();
-}
-
-struct LinkEmuTransport final : Transport {
-  int nranks = 1;
-  double link_gbps = 50.0, lat_us = 10.0, allreduce_us = 20.0;
-  int nwg = 8;
-  static double env(const char* k, double d) {
-    const char* e = std::getenv(k);
-    return e ? std::atof(e) : d;
-  }
-  LinkEmuTransport() {
-    link_gbps = env("BDX_EMU_LINK_GBPS", 50.0);
-    lat_us = env("BDX_EMU_LINK_LAT_US", 10.0);
-    allreduce_us = env("BDX_EMU_ALLREDUCE_US", 20.0);
-    nwg = static_cast<int>(env("BDX_EMU_LINK_WG", 8));
-    if (nwg < 1) nwg = 1;
-  }
-  // modelled link time of one exchange, microseconds
-  double exchange_us(const std::vector<int64_t>& scnt, const std::vector<int64_t>& rcnt,
-                     int esize) const {
-    int64_t worst = 0;
-    for (size_t p = 0; p < scnt.size() && p < rcnt.size(); ++p)
-      worst = std::max(worst, std::max(scnt[p], rcnt[p]) * esize);
-    if (worst == 0) return 0.0;
-    return worst / (link_gbps * 1e3) + lat_us;  // bytes / (1e3 link_gbps) = us
-  }
-  int exchange(const void* sbuf, const std::vector<int64_t>& scnt,
-               const std::vector<int64_t>& soff, void* rbuf, const std::vector<int64_t>& rcnt,
-               const std::vector<int64_t>& roff, int esize, hipStream_t st) override {
-    (void)soff;
-    (void)roff;
-    int64_t ns = 0, nr = 0;
-    for (int64_t c : scnt) ns += c;
-    for (int64_t c : rcnt) nr += c;
-    const double us = exchange_us(scnt, rcnt, esize);
-    if (us <= 0.0) return 0;
-    const int64_t n16 = std::min(ns, nr) * esize / 16;
-    hipLaunchKernelGGL(bdx_link_emu_kernel, dim3(nwg), dim3(256), 0, st,
-                       static_cast<const uint4*>(sbuf), static_cast<uint4*>(rbuf), n16,
-                       static_cast<int64_t>(us * 100.0));
-    return static_cast<int>(hipGetLastError());
-  }
-  int allreduce_sum(double*, int, hipStream_t st) override {
-    hipLaunchKernelGGL(bdx_link_emu_kernel, dim3(1), dim3(256), 0, st, nullptr, nullptr,
-                       int64_t{0}, static_cast<int64_t>(allreduce_us * 100.0));
-    return static_cast<int>(hipGetLastError());
-  }
-  bool capturable() const override { return true; }
-  int ranks() const override { return nranks; }
-};
-
-// Single rank: no communication at all.
-struct NoTransport final : Transport {
-  int exchange(const void*, const std::vector<int64_t>&, const std::vector<int64_t>&, void*,
-               const std::vector<int64_t>&, const std::vector<int64_t>&, int,
-               hipStream_t) override {
-    return 0;
-  }
-  int allreduce_sum(double*, int, hipStream_t) override { return 0; }
-  bool capturable() const override { return true; }
-  int ranks() const override { return 1; }
-};
-
-// R ranks = R threads of one process on one device (tests): host barriers,
-// device-to-device copies from the peers' posted buffers, fixed-order sums.
-struct ThreadGroupState {
-  std::mutex m;
-  std::condition_variable cv;
-  int size = 0, arrived = 0;
-  long generation = 0;
-  std::vector<const void*> sbuf;
-  std::vector<const std::vector<int64_t>*> soff;
-  std::vector<hipEvent_t> packed, copied;
-  std::vector<double*> red;
-  void barrier() {
-    std::unique_lock<std::mutex> lk(m);
-    const long gen = generation;
-    if (++arrived == size) {
-      arrived = 0;
-      ++generation;
-      cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return generation != gen; });
-    }
-  }
-};
-std::mutex g_groups_m;
-std::map<int64_t, std::shared_ptr<ThreadGroupState>> g_groups;
-
-// The exchange is stream-ordered, as RCCL's: the host only swaps buffer
-// pointers and event handles at two barriers and never waits for the device,
-// so the compute stream's interior tiles really run while the copies do.
-//   1. record `packed` on the caller's stream (after the pack kernel);
-//   2. barrier: every rank's send buffer / offsets / `packed` are published;
-//   3. per peer: wait for its `packed`, copy its slice into the receive buffer;
-//      record `copied`;
-//   4. barrier: every `copied` is published; wait for the `copied` of each
-//      peer that reads this rank's send buffer, so a later write to it (the
-//      next pack, stream-ordered after this) cannot overtake their copies.
-// Event reuse is safe: a rank re-records `packed` only after barrier 2 of
-// the previous exchange (every peer's wait on it was issued before that
-// barrier) and `copied` only after barrier 1 of the next exchange (every
-// peer issues its wait on it before arriving there).
-struct ThreadTransport final : Transport {
-  std::shared_ptr<ThreadGroupState> g;
-  int rank = 0;
-  hipEvent_t ev_packed = nullptr, ev_copied = nullptr;
-  ~ThreadTransport() override {
-    if (ev_packed) hipEventDestroy(ev_packed);
-    if (ev_copied) hipEventDestroy(ev_copied);
-  }
-  int exchange(const void* sbuf, const std::vector<int64_t>& scnt,
-               const std::vector<int64_t>& soff, void* rbuf, const std::vector<int64_t>& rcnt,
-               const std::vector<int64_t>& roff, int esize, hipStream_t st) override {
-    if (!ev_packed) {
-      BDX_CHECK(hipEventCreateWithFlags(&ev_packed, hipEventDisableTiming));
-      BDX_CHECK(hipEventCreateWithFlags(&ev_copied, hipEventDisableTiming));
-    }
-    BDX_CHECK(hipEventRecord(ev_packed, st));
-    g->sbuf[rank] = sbuf;
-    g->soff[rank] = &soff;
-    g->packed[rank] = ev_packed;
-    g->barrier();
-    for (int p = 0; p < g->size; ++p) {
-      if (rcnt[p] <= 0) continue;
-      const char* src = static_cast<const char*>(g->sbuf[p]) + (*g->soff[p])[rank] * esize;
-      BDX_CHECK(hipStreamWaitEvent(st, g->packed[p], 0));
-      BDX_CHECK(hipMemcpyAsync(static_cast<char*>(rbuf) + roff[p] * esize, src, rcnt[p] * esize,
-                               hipMemcpyDeviceToDevice, st));
-    }
-    BDX_CHECK(hipEventRecord(ev_copied, st));
-    g->copied[rank] = ev_copied;
-    g->barrier();
-    for (int p = 0; p < g->size; ++p)
-      if (scnt[p] > 0) BDX_CHECK(hipStreamWaitEvent(st, g->copied[p], 0));
-    return 0;
-  }
-  int allreduce_sum(double* dev, int n, hipStream_t st) override {
-    BDX_CHECK(hipStreamSynchronize(st));
-    g->red[rank] = dev;
-    g->barrier();
-    std::vector<double> acc(n, 0.0), v(n);
-    for (int p = 0; p < g->size; ++p) {  // fixed rank order: deterministic
-      BDX_CHECK(hipMemcpy(v.data(), g->red[p], n * sizeof(double), hipMemcpyDeviceToHost));
-      for (int i = 0; i < n; ++i) acc[i] += v[i];
-    }
-    g->barrier();
-    BDX_CHECK(hipMemcpy(dev, acc.data(), n * sizeof(double), hipMemcpyHostToDevice));
-    g->barrier();
-    return 0;
-  }
-  bool capturable() const override { return false; }
-  int ranks() const override { return g->size; }
-};
 
 // ------------------------------------------------------------------ the CG loop
 constexpr int kRR0 = 0, kRR1 = 1, kPAP = 2;
@@ -1053,10 +646,7 @@ struct CGRuntime final : LoopBase {
   }
 
   int convert(int dir, T* lat, T* til, hipStream_t s) {
-    if constexpr (sizeof(T) == 8)
-      return bdx_layout_convert_f64(dir, cfg.latdT, lat, til, s);
-    else
-      return bdx_layout_convert_f32(dir, cfg.latdT, lat, til, s);
+    return BDX_TWIN(T, bdx_layout_convert)(dir, cfg.latdT, lat, til, s);
   }
   // tiled: bring the prologue's r and x (preconditioned: and z; once per
   // binding: dinv) into the tiled copies, p_old = 0
@@ -1074,12 +664,8 @@ struct CGRuntime final : LoopBase {
     return static_cast<int>(hipMemsetAsync(pat, 0, L.size() * sizeof(T), st));
   }
   int finalize_ghost(hipStream_t s) {
-    if constexpr (sizeof(T) == 8)
-      return bdx_fused_finalize_f64(wlatd, wy, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy, cfg.sz, 1,
-                                    s);
-    else
-      return bdx_fused_finalize_f32(wlatd, wy, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy, cfg.sz, 1,
-                                    s);
+    return BDX_TWIN(T, bdx_fused_finalize)(wlatd, wy, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
+                                           cfg.sz, 1, s);
   }
 
   // The fused operator of iteration k on the tile rectangle `rect` (null:
@@ -1162,35 +748,20 @@ struct CGRuntime final : LoopBase {
     mark(kMPap, st);
     if (precond()) {
       // r update + z = dinv . r; r.z -> nxt, r.r -> rr_slot
-      if (is_tiled) {
-        if constexpr (sizeof(T) == 8)
-          rc = bdx_pcg_update_tiled_f64(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal,
-                                        cur, kPAP, nxt, upart, wdinv, wz, rr_slot, upart_rr, st);
-        else
-          rc = bdx_pcg_update_tiled_f32(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal,
-                                        cur, kPAP, nxt, upart, wdinv, wz, rr_slot, upart_rr, st);
-      } else if constexpr (sizeof(T) == 8) {
-        rc = bdx_pcg_update_iface_f64(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
-                                      cfg.sz, scal, cur, kPAP, nxt, upart, wdinv, wz, rr_slot,
-                                      upart_rr, st);
-      } else {
-        rc = bdx_pcg_update_iface_f32(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
-                                      cfg.sz, scal, cur, kPAP, nxt, upart, wdinv, wz, rr_slot,
-                                      upart_rr, st);
-      }
-    } else if (is_tiled) {
-      if constexpr (sizeof(T) == 8)
-        rc = bdx_cg_update_tiled_f64(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal, cur,
-                                     kPAP, nxt, upart, st);
+      if (is_tiled)
+        rc = BDX_TWIN(T, bdx_pcg_update_tiled)(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz,
+                                               scal, cur, kPAP, nxt, upart, wdinv, wz, rr_slot,
+                                               upart_rr, st);
       else
-        rc = bdx_cg_update_tiled_f32(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal, cur,
-                                     kPAP, nxt, upart, st);
-    } else if constexpr (sizeof(T) == 8) {
-      rc = bdx_cg_update_iface_f64(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
-                                   cfg.sz, scal, cur, kPAP, nxt, upart, st);
+        rc = BDX_TWIN(T, bdx_pcg_update_iface)(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty,
+                                               cfg.ntz, cfg.sy, cfg.sz, scal, cur, kPAP, nxt, upart,
+                                               wdinv, wz, rr_slot, upart_rr, st);
+    } else if (is_tiled) {
+      rc = BDX_TWIN(T, bdx_cg_update_tiled)(wlatd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, scal,
+                                            cur, kPAP, nxt, upart, st);
     } else {
-      rc = bdx_cg_update_iface_f32(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz, cfg.sy,
-                                   cfg.sz, scal, cur, kPAP, nxt, upart, st);
+      rc = BDX_TWIN(T, bdx_cg_update_iface)(cfg.latd, cfg.own, r, y, yb, zb, cb, cfg.nty, cfg.ntz,
+                                            cfg.sy, cfg.sz, scal, cur, kPAP, nxt, upart, st);
     }
     if (rc) return rc;
     mark(kMUpd, st);
@@ -1216,19 +787,12 @@ struct CGRuntime final : LoopBase {
       // the write-back of the tiled x (one of five streams of the pass)
       const T* p2 = (two || two1) ? pprev : nullptr;
       const int mask = (two ? 1 : 0) | (two1 ? 2 : 0) | 4;  // tile colours with two terms
-      if constexpr (sizeof(T) == 8)
-        return bdx_flush_export_f64(cfg.latdT, x, wx, plast, p2, scal, last, kPAP, slot, -1, mask,
-                                    st);
-      else
-        return bdx_flush_export_f32(cfg.latdT, x, wx, plast, p2, scal, last, kPAP, slot, -1, mask,
-                                    st);
+      return BDX_TWIN(T, bdx_flush_export)(cfg.latdT, x, wx, plast, p2, scal, last, kPAP, slot, -1,
+                                           mask, st);
     }
     pend = pend1 = 0;
     auto one = [&](T* p, int num, int den) {
-      if constexpr (sizeof(T) == 8)
-        return bdx_xflush_f64(cfg.latd, cfg.own, x, p, scal, num, den, st);
-      else
-        return bdx_xflush_f32(cfg.latd, cfg.own, x, p, scal, num, den, st);
+      return BDX_TWIN(T, bdx_xflush)(cfg.latd, cfg.own, x, p, scal, num, den, st);
     };
     int rc = one(plast, last, kPAP);
     if (!rc && two) rc = one(pprev, slot, -1);
@@ -1378,18 +942,10 @@ struct DofCGRuntime final : LoopBase {
     T* pnew = (k % 2 == 0) ? pb : pa;
     T* const yz = zero ? yk(k + 1) : nullptr;
     int nb = 0;
-    int rc;
-    if constexpr (sizeof(T) == 8)
-      rc = bdx_dofmap_apply_yz_f64(cfg.P, cfg.nq, cfg.geom, 1, tab, cells, ncl, cfg.nvec, cdofs,
-                                   cverts, coords, flags, G, cfg.kappa, kc, r, pold, pnew, x,
-                                   yk(k), yz, scal, first ? -1 : cur, first ? -1 : nxt,
-                                   xlag ? nxt : -1, xlag ? kPAP : -1, part, &nb, s);
-    else
-      rc = bdx_dofmap_apply_yz_f32(cfg.P, cfg.nq, cfg.geom, 1, tab, cells, ncl, cfg.nvec, cdofs,
-                                   cverts, coords, flags, G, cfg.kappa, kc, r, pold, pnew, x,
-                                   yk(k), yz, scal, first ? -1 : cur, first ? -1 : nxt,
-                                   xlag ? nxt : -1, xlag ? kPAP : -1, part, &nb, s);
-    return rc;
+    return BDX_TWIN(T, bdx_dofmap_apply_yz)(
+        cfg.P, cfg.nq, cfg.geom, 1, tab, cells, ncl, cfg.nvec, cdofs, cverts, coords, flags, G,
+        cfg.kappa, kc, r, pold, pnew, x, yk(k), yz, scal, first ? -1 : cur, first ? -1 : nxt,
+        xlag ? nxt : -1, xlag ? kPAP : -1, part, &nb, s);
   }
 
   int step(long k, bool first, bool xlag, int /*xm*/) override {
@@ -1446,10 +1002,8 @@ struct DofCGRuntime final : LoopBase {
     if (nranks > 1 && (rc = tr->allreduce_sum(scal + kPAP, 1, st))) return rc;
     mark(kMPap, st);
     int nu = 0;
-    if constexpr (sizeof(T) == 8)
-      rc = bdx_dofmap_cg_update_z_f64(cfg.nvec, flags, r, yc, scal, cur, kPAP, upart, &nu, 0, st);
-    else
-      rc = bdx_dofmap_cg_update_z_f32(cfg.nvec, flags, r, yc, scal, cur, kPAP, upart, &nu, 0, st);
+    rc = BDX_TWIN(T, bdx_dofmap_cg_update_z)(cfg.nvec, flags, r, yc, scal, cur, kPAP, upart, &nu, 0,
+                                             st);
     if (rc || (rc = bdx_reduce_partials(upart, nu, scal, nxt, st))) return rc;
     mark(kMUpd, st);
     if (nranks > 1 && (rc = tr->allreduce_sum(scal + nxt, 1, st))) return rc;
@@ -1462,10 +1016,7 @@ struct DofCGRuntime final : LoopBase {
     pend = 0;
     const int last = ((it - 1) % 2 == 0) ? kRR0 : kRR1;
     T* plast = ((it - 1) % 2 == 0) ? pb : pa;  // p_new of the last iteration
-    if constexpr (sizeof(T) == 8)
-      return bdx_dofmap_xflush_f64(cfg.nvec, x, plast, scal, last, kPAP, st);
-    else
-      return bdx_dofmap_xflush_f32(cfg.nvec, x, plast, scal, last, kPAP, st);
+    return BDX_TWIN(T, bdx_dofmap_xflush)(cfg.nvec, x, plast, scal, last, kPAP, st);
   }
 };
 

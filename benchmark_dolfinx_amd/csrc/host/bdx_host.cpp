@@ -26,6 +26,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "../include/bdx_host_api.h"
 #include "../include/bdx_lattice.h"
 #include "../include/bdx_watchdog.h"
 
@@ -838,11 +839,7 @@ extern "C" {
 int bdx_host_version() { return 1; }
 
 #define BDX_HOST_API(T, SUF)                                                  \
-  void bdx_cpu_stiffness_##SUF(const int64_t* latd, int nq, const T* phi0,    \
-                               const T* dphi1, const T* wts, const T* qpts,   \
-                               const T* nodes, int identity, const T* xv,     \
-                               T kappa, const T* kc, const T* u, T* y,        \
-                               const int64_t* lo, const int64_t* hi) {        \
+  void bdx_cpu_stiffness_##SUF BDX_P_CPU_STIFFNESS(T) {                       \
     StiffArgs<T> a;                                                           \
     a.lat = BdxLattice::from(latd);                                           \
     a.tb = make_tables<T>(phi0, dphi1, wts, qpts, nodes, identity);           \
@@ -857,13 +854,7 @@ int bdx_host_version() { return 1; }
     }                                                                         \
     dispatch<Stiff<T>::template K>(static_cast<int>(a.lat.P), nq, a);         \
   }                                                                           \
-  /* the same with precomputed geometry factors G (null: on the fly) */       \
-  void bdx_cpu_stiffness_g_##SUF(const int64_t* latd, int nq, const T* phi0,  \
-                                 const T* dphi1, const T* wts, const T* qpts, \
-                                 const T* nodes, int identity, const T* xv,   \
-                                 const T* G, T kappa, const T* kc,            \
-                                 const T* u, T* y, const int64_t* lo,         \
-                                 const int64_t* hi) {                         \
+  void bdx_cpu_stiffness_g_##SUF BDX_P_CPU_STIFFNESS_G(T) {                   \
     StiffArgs<T> a;                                                           \
     a.lat = BdxLattice::from(latd);                                           \
     a.tb = make_tables<T>(phi0, dphi1, wts, qpts, nodes, identity);           \
@@ -879,36 +870,21 @@ int bdx_host_version() { return 1; }
     }                                                                         \
     dispatch<Stiff<T>::template K>(static_cast<int>(a.lat.P), nq, a);         \
   }                                                                           \
-  /* the reference data model on the CPU (dofmap_cells) */                   \
-  void bdx_cpu_dofmap_##SUF(int P, int nq, const T* phi0, const T* dphi1,     \
-                            const T* wts, const T* qpts, int identity,        \
-                            const int* cells, int ncl, const int* cdofs,      \
-                            const int* cverts, const T* coords, const T* G,   \
-                            const unsigned char* flags, T kappa, const T* kc, \
-                            const T* u, T* y) {                               \
+  void bdx_cpu_dofmap_##SUF BDX_P_CPU_DOFMAP(T) {                              \
     DofArgsCPU<T> a{make_tables<T>(phi0, dphi1, wts, qpts, nullptr, identity), \
                     cells, cdofs, cverts, ncl, coords, G, flags, kappa, kc,  \
                     u, y};                                                    \
     dispatch<DofmapCPU<T>::template K>(P, nq, a);                             \
   }                                                                           \
-  void bdx_cpu_dofmap_geometry_##SUF(int P, int nq, const T* wts,             \
-                                     const T* qpts, int ncells,               \
-                                     const int* cverts, const T* coords,      \
-                                     T* G) {                                  \
+  void bdx_cpu_dofmap_geometry_##SUF BDX_P_CPU_DOFMAP_GEOMETRY(T) {           \
     DofGeomArgs<T> a{ncells, cverts, coords, wts, qpts, G};                   \
     dispatch<DofGeomCPU<T>::template K>(P, nq, a);                            \
   }                                                                           \
-  /* geometry factors of every local cell, reference layout [c][6][nq^3] */  \
-  void bdx_cpu_geometry_##SUF(const int64_t* latd, int nq, const T* wts,      \
-                              const T* qpts, const T* xv, T* G) {             \
+  void bdx_cpu_geometry_##SUF BDX_P_CPU_GEOMETRY(T) {                         \
     GeomArgs<T> a{BdxLattice::from(latd), wts, qpts, xv, G};                  \
     dispatch<Geom<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
   }                                                                           \
-  void bdx_cpu_mass_##SUF(const int64_t* latd, int nq, const T* phi0,         \
-                          const T* dphi1, const T* wts, const T* qpts,        \
-                          const T* nodes, int identity, const T* xv,          \
-                          const T* f, T* b, const int64_t* lo,                \
-                          const int64_t* hi) {                                \
+  void bdx_cpu_mass_##SUF BDX_P_CPU_MASS(T) {                                 \
     MassArgs<T> a;                                                            \
     a.lat = BdxLattice::from(latd);                                           \
     a.tb = make_tables<T>(phi0, dphi1, wts, qpts, nodes, identity);           \
@@ -921,12 +897,7 @@ int bdx_host_version() { return 1; }
     }                                                                         \
     dispatch<Mass<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
   }                                                                           \
-  /* d += matrix-free diag(A) of the cells [lo, hi) (B = phi0, Dd = dphi1 */ \
-  /* phi0; Dirichlet dofs skipped): the host twin of bdx_diag */              \
-  void bdx_cpu_diag_##SUF(const int64_t* latd, int nq, const T* B,            \
-                          const T* Dd, const T* wts, const T* qpts,           \
-                          const T* xv, T kappa, const T* kc, T* d,            \
-                          const int64_t* lo, const int64_t* hi) {             \
+  void bdx_cpu_diag_##SUF BDX_P_CPU_DIAG(T) {                                 \
     DiagArgs<T> a;                                                            \
     a.lat = BdxLattice::from(latd);                                           \
     a.B = B;                                                                  \
@@ -943,17 +914,11 @@ int bdx_host_version() { return 1; }
     }                                                                         \
     dispatch<Diag<T>::template K>(static_cast<int>(a.lat.P), nq, a);          \
   }                                                                           \
-  int64_t bdx_cpu_csr_##SUF(const int64_t* latd, int nq, const T* B,          \
-                            const T* Dd, const T* wts, const T* qpts,         \
-                            const T* xv, T kappa, const T* kc,                \
-                            int64_t* row_ptr, int32_t* cols, T* vals,         \
-                            int count_only) {                                 \
+  int64_t bdx_cpu_csr_##SUF BDX_P_CPU_CSR(T) {                                \
     return csr_build<T>(latd, nq, B, Dd, wts, qpts, xv, kappa, kc, row_ptr,   \
                         cols, vals, count_only);                              \
   }                                                                           \
-  void bdx_cpu_spmv_##SUF(int64_t nrows, const int64_t* beg, const int64_t* end, \
-                          const int32_t* cols, const T* vals, const T* x,     \
-                          T* y, int acc) {                                    \
+  void bdx_cpu_spmv_##SUF BDX_P_CPU_SPMV(T) {                                 \
     _Pragma("omp parallel for schedule(static)") for (int64_t r = 0;          \
                                                       r < nrows; ++r) {       \
       T s = 0;                                                                \
@@ -961,9 +926,7 @@ int bdx_host_version() { return 1; }
       y[r] = acc ? y[r] + s : s;                                              \
     }                                                                         \
   }                                                                           \
-  /* f = 1000 exp(-((x-1/2)^2 + (y-1/2)^2)/0.02) at the physical dof nodes */ \
-  void bdx_cpu_interp_f_##SUF(const int64_t* latd, const T* nodes,            \
-                              const T* xv, T* f) {                            \
+  void bdx_cpu_interp_f_##SUF BDX_P_CPU_INTERP_F(T) {                         \
     const BdxLattice lat = BdxLattice::from(latd);                            \
     const int64_t P = lat.P;                                                  \
     _Pragma("omp parallel for collapse(2)") for (int64_t i = 0;               \

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 
+#include "../include/bdx_host_api.h"
 #include "../include/bdx_lattice.h"
 #include "../include/bdx_mg_bodies.h"
 #include "../include/bdx_pmg_tail.h"
@@ -261,49 +262,26 @@ int pmg_tail_host(const int64_t* tab, int nlev, int64_t nwords, const T* r, T* z
 extern "C" {
 
 #define BDX_HOST_MG_API(T, SUF)                                               \
-  /* p-multigrid transfers between the coarse and fine lattices latc / latf */ \
-  /* (J: the (Pf + 1) x (Pc + 1) 1D table): vf = P vc, vc += P^T vf; the   */ \
-  /* host twins of bdx_prolong / bdx_restrict, nonzero for a bad pair      */ \
-  int bdx_cpu_prolong_##SUF(const int64_t* latc, const int64_t* latf,         \
-                            const double* J, const T* vc, T* vf) {            \
+  int bdx_cpu_prolong_##SUF BDX_P_CPU_PROLONG(T) {                            \
     return prolong_host<T>(latc, latf, J, vc, vf);                            \
   }                                                                           \
-  int bdx_cpu_restrict_##SUF(const int64_t* latc, const int64_t* latf,        \
-                             const double* J, const T* vf, T* vc) {           \
+  int bdx_cpu_restrict_##SUF BDX_P_CPU_RESTRICT(T) {                          \
     return restrict_host<T>(latc, latf, J, vf, vc);                           \
   }                                                                           \
-  /* h-multigrid transfers between the degree-1 lattices latc / latf with   */ \
-  /* the tables cidx, cw, fpos: vf (+)= P vc, vc = P^T (vf - y); the host    */ \
-  /* twins of bdx_hprolong / bdx_hrestrict, nonzero for a bad pair          */ \
-  int bdx_cpu_hprolong_##SUF(const int64_t* latc, const int64_t* latf,        \
-                             const int* cidx, const T* cw, const int* fpos,   \
-                             const T* vc, T* vf, int add) {                   \
+  int bdx_cpu_hprolong_##SUF BDX_P_CPU_HPROLONG(T) {                          \
     return hprolong_host<T>(latc, latf, cidx, cw, fpos, vc, vf, add);         \
   }                                                                           \
-  int bdx_cpu_hrestrict_##SUF(const int64_t* latc, const int64_t* latf,       \
-                              const int* cidx, const T* cw, const int* fpos,  \
-                              const T* vf, const T* y, T* vc) {               \
+  int bdx_cpu_hrestrict_##SUF BDX_P_CPU_HRESTRICT(T) {                        \
     return hrestrict_host<T>(latc, latf, cidx, cw, fpos, vf, y, vc);          \
   }                                                                           \
-  /* Chebyshev step d = a d + b dinv (r - y); z += d (first: d = z = b dinv */ \
-  /* r), the host twin of bdx_cheb_step                                    */ \
-  void bdx_cpu_cheb_step_##SUF(int64_t L1, int64_t ld, int64_t o0,            \
-                               int64_t o1, int64_t o2, int first, double a,   \
-                               double b, const T* dinv, const T* r,           \
-                               const T* y, T* d, T* z) {                      \
+  void bdx_cpu_cheb_step_##SUF BDX_P_CPU_CHEB_STEP(T) {                       \
     cheb_step_host<T>(L1, ld, o0, o1, o2, first, static_cast<T>(a),           \
                       static_cast<T>(b), dinv, r, y, d, z);                   \
   }                                                                           \
-  /* the V-cycle from the first level of the table (bdx_pmg_tail.h) down and */ \
-  /* back up, z = M r: the host twin of bdx_pmg_tail, nonzero for a bad table */ \
-  int bdx_cpu_pmg_tail_##SUF(const int64_t* tab, int nlev, int64_t nwords,    \
-                             const T* r, T* z) {                              \
+  int bdx_cpu_pmg_tail_##SUF BDX_P_CPU_PMG_TAIL(T) {                          \
     return pmg_tail_host<T>(tab, nlev, nwords, r, z);                         \
   }                                                                           \
-  /* y = A z with the 27-point stencil S of the degree-1 lattice latd (the  */ \
-  /* tail's operator, alone)                                                */ \
-  void bdx_cpu_stencil27_##SUF(const int64_t* latd, const T* S, const T* z,   \
-                               T* y) {                                        \
+  void bdx_cpu_stencil27_##SUF BDX_P_CPU_STENCIL27(T) {                       \
     stencil_host<T>(BdxLattice::from(latd), S, z, y);                         \
   }
 

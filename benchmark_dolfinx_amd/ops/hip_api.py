@@ -1,4 +1,5 @@
-"""ctypes signatures of libbdx_hip.so (see csrc/hip/*.hip)."""
+"""ctypes signatures of libbdx_hip.so, one row per prototype of
+csrc/include/bdx_hip_api.h (tests/test_api_signatures.py compares the two)."""
 
 from __future__ import annotations
 
@@ -10,6 +11,10 @@ i64 = ctypes.c_int64
 f64 = ctypes.c_double
 f32 = ctypes.c_float
 
+# degrees with a per-degree operator instance (BDX_FUSED_DEGREES / BDX_FUSED5_DEGREES)
+FUSED_DEGREES = range(1, 8)
+FUSED5_DEGREES = range(3, 8)
+
 
 def _d(lib, name, argtypes, restype=i32):
     fn = getattr(lib, name)
@@ -20,8 +25,8 @@ def _d(lib, name, argtypes, restype=i32):
 def declare(lib) -> None:
     _d(lib, "bdx_hip_partials_size", [])
     _d(lib, "bdx_device_info", [i32, ctypes.c_char_p, i32])
+    _d(lib, "bdx_build_debug", [])
     for suf in ("f64", "f32"):
-        ft = f64 if suf == "f64" else f32
         _d(lib, f"bdx_dot_{suf}", [i64, i64, i64, i64, i64, vp, vp, vp, vp, i32, vp])
         _d(lib, f"bdx_cg_update_{suf}",
            [i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp])
@@ -53,15 +58,15 @@ def declare(lib) -> None:
         _d(lib, f"bdx_dofmap_xflush_{suf}", [i64, vp, vp, vp, i32, i32, vp])
         _d(lib, f"bdx_dofmap_geometry_{suf}", [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp])
         _d(lib, f"bdx_spmv_{suf}", [i64, vp, vp, vp, vp, vp, vp, i32, vp])
-        for P in range(1, 8):
+        for P in FUSED_DEGREES:
             name = f"bdx_fused_apply_{suf}_p{P}"
             if hasattr(lib, name):
                 _d(lib, name, [i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                vp, vp, vp, vp, f64, vp, vp, i32, i32, i32, i32, vp])
-        for P, v in [(P, v) for P in range(1, 8) for v in (2, 3)]:
+        for P, v in [(P, v) for P in FUSED_DEGREES for v in (2, 3)]:
             if hasattr(lib, f"bdx_fused{v}_segments_{suf}_p{P}"):
                 _d(lib, f"bdx_fused{v}_segments_{suf}_p{P}", [i32, i32, i32, i32])
-        for P, v in [(P, v) for P in range(1, 8) for v in (2, 3, 4, 5)]:
+        for P, v in [(P, v) for v in (2, 3) for P in FUSED_DEGREES] + [(P, 5) for P in FUSED5_DEGREES]:
             name = f"bdx_fused{v}_apply_{suf}_p{P}"
             if hasattr(lib, name):
                 _d(lib, name, [i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -79,7 +84,7 @@ def declare(lib) -> None:
         _d(lib, f"bdx_flush_export_{suf}", [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp])
         _d(lib, f"bdx_fused_tables_{suf}", [i32, i32, vp, vp, vp])
         _d(lib, f"bdx_fused3_tables_{suf}", [i32, i32, vp, vp, vp])
-        for P in range(1, 8):
+        for P in FUSED5_DEGREES:
             if hasattr(lib, f"bdx_fused5_tables_{suf}_p{P}"):
                 _d(lib, f"bdx_fused5_tables_{suf}_p{P}", [i32, i32, vp, vp, vp, vp])
                 _d(lib, f"bdx_fused5_tile_p{P}_{suf}", [i32, vp, vp])
@@ -121,4 +126,3 @@ def declare(lib) -> None:
     _d(lib, "bdx_rt_release_group", [i64], None)
     _d(lib, "bdx_reduce_partials", [vp, i32, vp, i32, vp])
     _d(lib, "bdx_dofmap_mark_writers", [vp, i32, vp, i32, vp, i32, vp, i64, vp])
-    del ft

@@ -24,12 +24,6 @@ _host = None
 _hip = None
 _loaded = {}
 
-vp = ctypes.c_void_p
-i32 = ctypes.c_int
-i64 = ctypes.c_int64
-f64 = ctypes.c_double
-f32 = ctypes.c_float
-
 
 def ptr(x) -> int:
     """Raw data pointer of a torch tensor or numpy array (None -> 0).
@@ -46,13 +40,6 @@ def ptr(x) -> int:
     return x.data_ptr()
 
 
-def _declare(lib, name, argtypes, restype=None):
-    fn = getattr(lib, name)
-    fn.argtypes = argtypes
-    fn.restype = restype
-    return fn
-
-
 def host():
     """The host runtime library (built on first use)."""
     global _host
@@ -62,35 +49,8 @@ def host():
             path = os.environ.get("BDX_HOST_LIB") or _build.build_host()
             lib = ctypes.CDLL(str(path))
             _loaded["host"] = str(path)
-            for suf, ft in (("f64", f64), ("f32", f32)):
-                _declare(lib, f"bdx_cpu_stiffness_{suf}",
-                         [vp, i32, vp, vp, vp, vp, vp, i32, vp, ft, vp, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_stiffness_g_{suf}",
-                         [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, ft, vp, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_geometry_{suf}", [vp, i32, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_dofmap_{suf}",
-                         [i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, ft, vp,
-                          vp, vp])
-                _declare(lib, f"bdx_cpu_dofmap_geometry_{suf}", [i32, i32, vp, vp, i32, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_mass_{suf}",
-                         [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_diag_{suf}",
-                         [vp, i32, vp, vp, vp, vp, vp, ft, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_csr_{suf}",
-                         [vp, i32, vp, vp, vp, vp, vp, ft, vp, vp, vp, vp, i32], i64)
-                _declare(lib, f"bdx_cpu_spmv_{suf}", [i64, vp, vp, vp, vp, vp, vp, i32])
-                _declare(lib, f"bdx_cpu_interp_f_{suf}", [vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_prolong_{suf}", [vp, vp, vp, vp, vp], i32)
-                _declare(lib, f"bdx_cpu_restrict_{suf}", [vp, vp, vp, vp, vp], i32)
-                _declare(lib, f"bdx_cpu_hprolong_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32], i32)
-                _declare(lib, f"bdx_cpu_hrestrict_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp], i32)
-                _declare(lib, f"bdx_cpu_cheb_step_{suf}",
-                         [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
-                _declare(lib, f"bdx_cpu_pmg_tail_{suf}", [vp, i32, i64, vp, vp], i32)
-                _declare(lib, f"bdx_cpu_stencil27_{suf}", [vp, vp, vp, vp])
-            # the precision boundary of the mixed multigrid solve
-            _declare(lib, "bdx_cpu_demote_f64_f32", [i64, i64, i64, i64, i64, vp, vp])
-            _declare(lib, "bdx_cpu_promote_f32_f64", [i64, i64, i64, i64, i64, vp, vp])
+            from . import host_api
+            host_api.declare(lib)
             _host = lib
     return _host
 
@@ -124,10 +84,7 @@ def build_flags() -> dict:
     valid: the arch, the library file, and whether it is the production build
     (the in-tree libbdx_hip.so, built with no extra flags) rather than an
     A/B variant (BDX_HIP_LIB) or a bounds-checked debug build (BDX_DEBUG)."""
-    lib = hip()
-    fn = lib.bdx_build_debug
-    fn.restype = ctypes.c_int
-    debug = int(fn())
+    debug = int(hip().bdx_build_debug())
     path = _loaded.get("hip", "")
     production = os.path.abspath(path) == os.path.abspath(str(_build.HIP_SO))
     return {"arch": _build.HIP_ARCH, "hiplib": os.path.basename(path), "debug": debug,

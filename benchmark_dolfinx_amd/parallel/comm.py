@@ -182,7 +182,7 @@ class EmulatedRankComm(Comm):
     The problem is that rank's block of the N-rank partition, ghost planes
     included, so the operator and the native runtime's split schedule run
     exactly as on the rank of a real N-GPU run; the native runtime replaces
-    RCCL by modelled link times (runtime.hip LinkEmuTransport).  Host-side
+    RCCL by modelled link times (csrc/hip/rt_transport.h LinkEmuTransport).  Host-side
     collectives are local no-ops: all-reduces return the rank's own values
     and all-to-alls deliver zeros, so norms are this rank's, not the global
     problem's -- for timing the schedule, not for results.
