@@ -20,8 +20,7 @@ constexpr int kMaxNq = 9;
 // v1 TAB for nd=8, nq=9 at the f32 pitch); the runtime copies this many
 // entries
 constexpr int kFusedTabMax = 2 * 9 * 12 + 9 * 8 + 8 * 12;
-
-enum { kGeomStored = 0, kGeomOTF = 1 };
+// kGeomStored / kGeomOTF: bdx_rt_setup.h (through bdx_hip_api.h)
 
 // FP64 MFMA operand / accumulator vectors (v_mfma_f64_16x16x4f64: 4 results per lane)
 typedef double bdx_f64x4 __attribute__((ext_vector_type(4)));

@@ -29,8 +29,7 @@
 #pragma once
 #include "bdx_common.h"
 
-enum { kFusedAction = 0, kFusedCG = 1 };
-
+// kFusedAction / kFusedCG: bdx_hip_api.h, with the fused apply's mode word
 
 // 1/x from the hardware reciprocal estimate + two Newton steps (full
 // precision for the normal, positive Jacobian determinants seen here) instead

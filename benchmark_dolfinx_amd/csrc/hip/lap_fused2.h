@@ -889,7 +889,7 @@ inline int fused_set_rect(Fused2Args<T>& a, const int* rect) {
 // layer's planes belong to the previous segment).  No inter-workgroup
 // synchronisation, bitwise identical to S = 1 except for the order of the
 // p.Ap partial sums (one per work item).
-//   mode argument of the apply entry points: kind | (S << 8), S = 0 -> 1.
+//   S travels in the apply entry points' mode word (fused_mode_pack), 0 -> 1.
 inline int fused_choose_segments(int tiles, int ncx, int resident) {
   if (tiles <= 0 || ncx <= 1 || resident <= 0) return 1;
   int best = 1;
@@ -927,7 +927,7 @@ inline int fused_set_segments(Fused2Args<T>& a, int nseg) {
 
 // Host-side launch prologue of the fused2 / fused3 / fused5 apply entry points
 // (BDX_P_FUSED_APPLY, bdx_hip_api.h): the argument block from the lattice
-// descriptor, the tile rectangle, the x segments (mode bits 8-15) and the entry
+// descriptor, the tile rectangle, the x segments of the mode word and the entry
 // point's vectors, scalar slots and kappa.  What differs between the three
 // (tiled storage, x-mode bits, tables) stays at their call sites.
 template <typename T>
@@ -937,7 +937,7 @@ int fill_fused2_args(Fused2Args<T>& a, int mode, const int64_t* latd, int nty, i
                      double* partials, int beta_num, int beta_den, int xa_num, int xa_den) {
   BDX_CHECK(static_cast<hipError_t>(make_fused2_args(a, latd, nty, ntz)));
   BDX_CHECK(static_cast<hipError_t>(fused_set_rect(a, rect)));
-  BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, (mode >> 8) & 0xff)));
+  BDX_CHECK(static_cast<hipError_t>(fused_set_segments(a, fused_mode_nseg(mode))));
   a.u = u;
   a.pold = pold;
   a.pnew = pnew;
@@ -967,7 +967,7 @@ int fill_fused2_args(Fused2Args<T>& a, int mode, const int64_t* latd, int nty, i
     Fused2Args<T> a;                                                               \
     BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
     if (a.tsy) return static_cast<int>(hipErrorInvalidValue); /* lattice layout only */ \
-    mode &= 0xff;                                                                  \
+    mode = fused_mode_kind_nox(mode);                                              \
     if (!tabs) return static_cast<int>(hipErrorInvalidValue);                      \
     FusedTables<T> tb;                                                             \
     for (int i = 0; i < kFusedTabMax; ++i) tb.tab[i] = tabs[i];                    \

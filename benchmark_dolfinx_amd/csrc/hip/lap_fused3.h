@@ -1340,7 +1340,7 @@ int fused3_resident(int affine) {
   extern "C" int bdx_fused3_apply_##SUF##_p##PP BDX_P_FUSED_APPLY(T) {             \
     Fused2Args<T> a;                                                               \
     BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
-    mode &= 0xff;                                                                  \
+    mode = fused_mode_kind_nox(mode);                                              \
     if (!tabs) return static_cast<int>(hipErrorInvalidValue);                      \
     FusedTables<T> tb;                                                             \
     for (int i = 0; i < kFusedTabMax; ++i) tb.tab[i] = tabs[i];                    \

@@ -1046,11 +1046,11 @@ int launch_fused5(int affine_ok, const Fused2Args<T>& a, const T* tabd, hipStrea
     if (!affine_ok || !tabs) return static_cast<int>(hipErrorInvalidValue);        \
     Fused2Args<T> a;                                                               \
     BDX_CHECK(static_cast<hipError_t>(fill_fused2_args<T>(BDX_FUSED_FILL_ARGS)));  \
-    a.xmode = (mode >> 4) & 3;                                                     \
-    a.xmode1 = ((mode >> 6) & 3) - 1;                                              \
-    a.xslot_w = kScalXSave + ((mode >> 16) & 1);                                   \
-    a.xslot_r = kScalXSave + ((mode >> 17) & 1);                                   \
-    mode &= 0xf;                                                                   \
+    a.xmode = fused_mode_xmode(mode);                                              \
+    a.xmode1 = fused_mode_xmode1(mode);                                            \
+    a.xslot_w = kScalXSave + fused_mode_xsave_w(mode);                             \
+    a.xslot_r = kScalXSave + fused_mode_xsave_r(mode);                             \
+    mode = fused_mode_kind(mode);                                                  \
     const T* tabd = tabs; /* device pointer: the operator's own table buffer */   \
     return mode == kFusedCG ? launch_fused5<T, PP + 1, kFusedCG>(affine_ok, a, tabd, st) \
                             : launch_fused5<T, PP + 1, kFusedAction>(affine_ok, a, tabd, st); \

@@ -254,12 +254,10 @@ struct LoopBase {
   }
 
   // Streams, events, halo tables and the transport (every runtime kind).
-  // ptrs: hbuf_a, hbuf_b, face_boxes, ghost_boxes.
-  int init_common(hipStream_t ext_stream, void* const* hptrs, const int64_t* halo_sizes,
-                  const int64_t* fcnt, const int64_t* gcnt, int transport, int n, int r,
-                  int64_t group_id) {
+  int init_common(hipStream_t ext_stream, const BdxRtHalo& h) {
+    const int n = h.nranks;
     nranks = n;
-    rank = r;
+    rank = h.rank;
     ext = ext_stream;
     // The comm stream runs at the greatest priority the device offers: its
     // chain (RCCL send/recv kernels, the boundary work, the reverse send) is
@@ -274,16 +272,16 @@ struct LoopBase {
     BDX_CHECK(hipStreamGetPriority(cs, &prio_cs));
     for (hipEvent_t* e : {&ev_in, &ev_out, &ev_fork, &ev_rev, &ev_batch[0], &ev_batch[1]})
       BDX_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    hbuf_a = hptrs[0];
-    hbuf_b = hptrs[1];
-    face_boxes = static_cast<const int64_t*>(hptrs[2]);
-    ghost_boxes = static_cast<const int64_t*>(hptrs[3]);
-    nface_boxes = static_cast<int>(halo_sizes[0]);
-    face_total = halo_sizes[1];
-    nghost_boxes = static_cast<int>(halo_sizes[2]);
-    ghost_total = halo_sizes[3];
-    face_cnt.assign(fcnt, fcnt + n);
-    ghost_cnt.assign(gcnt, gcnt + n);
+    hbuf_a = h.buf_a;
+    hbuf_b = h.buf_b;
+    face_boxes = h.face_boxes;
+    ghost_boxes = h.ghost_boxes;
+    nface_boxes = h.nface_boxes;
+    face_total = h.face_total;
+    nghost_boxes = h.nghost_boxes;
+    ghost_total = h.ghost_total;
+    face_cnt.assign(h.face_cnt, h.face_cnt + n);
+    ghost_cnt.assign(h.ghost_cnt, h.ghost_cnt + n);
     face_off.assign(n, 0);
     ghost_off.assign(n, 0);
     for (int p = 1; p < n; ++p) {
@@ -291,15 +289,15 @@ struct LoopBase {
       ghost_off[p] = ghost_off[p - 1] + ghost_cnt[p - 1];
     }
     halo = n > 1 && (face_total + ghost_total) > 0;
-    if (transport == 1 && n > 1) {  // RCCL: connected by bdx_rt_connect
+    if (h.transport == kBdxTransportRccl && n > 1) {  // connected by bdx_rt_connect
       auto t = std::make_unique<RcclTransport>();
       t->nranks = n;
       tr = std::move(t);
-    } else if (transport == 2 && n > 1) {  // in-process threads
+    } else if (h.transport == kBdxTransportThread && n > 1) {  // in-process threads
       auto t = std::make_unique<ThreadTransport>();
       {
         std::lock_guard<std::mutex> lk(g_groups_m);
-        auto& g = g_groups[group_id];
+        auto& g = g_groups[h.group_id];
         if (!g) {
           g = std::make_shared<ThreadGroupState>();
           g->size = n;
@@ -311,9 +309,9 @@ struct LoopBase {
         }
         t->g = g;
       }
-      t->rank = r;
+      t->rank = h.rank;
       tr = std::move(t);
-    } else if (transport == 3 && n > 1) {  // emulated links (one rank alone)
+    } else if (h.transport == kBdxTransportEmulated && n > 1) {  // emulated links (one rank alone)
       auto t = std::make_unique<LinkEmuTransport>();
       t->nranks = n;
       tr = std::move(t);
@@ -469,14 +467,12 @@ struct LoopBase {
     return flush();
   }
 
-  // n eager iterations with timing events between the phases; out[i] = mean
-  // ms of interval i (see bdx_rt_profile for the list).
-  static constexpr int kNPhases = 13;
-  int profile(long n, double* out, int nout) {
-    if (nout < kNPhases) return static_cast<int>(hipErrorInvalidValue);
+  // n eager iterations with timing events between the phases; *out = mean ms
+  // of every interval (BdxRtPhases, bdx_rt_setup.h).
+  int profile(long n, BdxRtPhases* out) {
     for (int i = 0; i < kNMarks; ++i)
       if (!pev[i]) BDX_CHECK(hipEventCreate(&pev[i]));
-    for (int i = 0; i < nout; ++i) out[i] = 0.0;
+    *out = BdxRtPhases{};
     BDX_CHECK(hipEventRecord(ev_in, ext));
     BDX_CHECK(hipStreamWaitEvent(st, ev_in, 0));
     // prof is cleared on every exit path (an early error return must not
@@ -503,40 +499,43 @@ struct LoopBase {
         (void)hipEventElapsedTime(&ms, pev[a], pev[b]);
         return static_cast<double>(ms);
       };
-      out[0] += dt(kMFwdBeg, kMFwdEnd);
-      out[1] += dt(kMStart, kMOpA);
+      out->halo_fwd += dt(kMFwdBeg, kMFwdEnd);
+      out->op_interior += dt(kMStart, kMOpA);
       // split: forward-halo end -> boundary work; serial: the boundary work
       // only (kMFwdEnd precedes the whole operator there)
-      out[2] += split ? dt(kMFwdEnd, kMBnd) : dt(kMOpA, kMBnd);
-      out[3] += dt(kMRevBeg, kMRevEnd);
-      out[4] += dt(kMOpA, kMJoin);
-      out[5] += dt(kMJoin, kMPap);
-      out[6] += dt(kMPap, kMUpd);
-      out[7] += dt(kMUpd, kMEnd);
-      out[8] += dt(kMStart, kMEnd);
+      out->op_boundary += split ? dt(kMFwdEnd, kMBnd) : dt(kMOpA, kMBnd);
+      out->halo_rev += dt(kMRevBeg, kMRevEnd);
+      out->join_rev_add += dt(kMOpA, kMJoin);
+      out->reduce_allreduce_pap += dt(kMJoin, kMPap);
+      out->update_rr += dt(kMPap, kMUpd);
+      out->allreduce_rr += dt(kMUpd, kMEnd);
+      out->iteration += dt(kMStart, kMEnd);
       // timeline offsets from the iteration start: the comm-stream chain is
       // hidden when it completes before the interior work does
-      out[9] += dt(kMStart, kMFwdEnd);
-      out[10] += dt(kMStart, kMBnd);
-      out[11] += dt(kMStart, kMRevEnd);
-      out[12] += dt(kMStart, kMOpA);
+      out->t_halo_fwd_done += dt(kMStart, kMFwdEnd);
+      out->t_boundary_done += dt(kMStart, kMBnd);
+      out->t_halo_rev_done += dt(kMStart, kMRevEnd);
+      out->t_op_interior_done += dt(kMStart, kMOpA);
     }
     prof = false;
     if (!rc) rc = flush();
     BDX_CHECK(hipEventRecord(ev_out, st));
     BDX_CHECK(hipStreamWaitEvent(ext, ev_out, 0));
-    for (int i = 0; i < kNPhases && n > 0; ++i) out[i] /= static_cast<double>(n);
+    // the record is doubles and nothing else (tests/test_abi_layouts.py)
+    double* const ms = reinterpret_cast<double*>(out);
+    for (size_t i = 0; i < sizeof(BdxRtPhases) / sizeof(double) && n > 0; ++i)
+      ms[i] /= static_cast<double>(n);
     return rc;
   }
 
   // Pre-flight of the transport before any timed work (bench.py at N > 1):
   // one forward halo exchange of the loop's halo vector and a device
   // all-reduce of (rank + 1), under a deadline of timeout_s instead of the
-  // run's.  out[0] = host ms of both, out[1] = the all-reduce result
+  // run's.  out->ms = host ms of both, out->allreduce = the all-reduce result
   // (n (n + 1) / 2 when every rank took part).  A peer that never joins
   // aborts the communicator: the error comes back here instead of a hang
   // inside the warmup.
-  int preflight(double timeout_s, double* out) {
+  int preflight(double timeout_s, BdxRtPreflight* out) {
     if (!pf_scal) BDX_CHECK(hipMalloc(&pf_scal, sizeof(double)));
     const double v = rank + 1.0;
     bdx::Watchdog* wd = tr->watchdog();
@@ -562,8 +561,8 @@ struct LoopBase {
     }
     if (!rc) rc = tr->wait(ev_out);
     if (rc) return rc;
-    out[0] = (bdx::Watchdog::now_ns() - t0) * 1e-6;
-    BDX_CHECK(hipMemcpy(&out[1], pf_scal, sizeof(double), hipMemcpyDeviceToHost));
+    out->ms = (bdx::Watchdog::now_ns() - t0) * 1e-6;
+    BDX_CHECK(hipMemcpy(&out->allreduce, pf_scal, sizeof(double), hipMemcpyDeviceToHost));
     BDX_CHECK(hipStreamWaitEvent(ext, ev_out, 0));
     return 0;
   }
@@ -571,8 +570,8 @@ struct LoopBase {
 
 // ---------------------------------------------------- fused structured operator
 struct RtConfig {
-  int64_t latd[21];
-  int64_t latdT[21];  // tiled-storage descriptor (tsy = 0: lattice layout)
+  int64_t latd[kLatticeWords];
+  int64_t latdT[kLatticeWords];  // tiled-storage descriptor (tsy = 0: lattice layout)
   int64_t own[3];
   int version, affine, P, nq, nblocks, nty, ntz, sy, sz, nseg;
   double kappa;
@@ -586,7 +585,7 @@ struct CGRuntime final : LoopBase {
   std::vector<T> tabs_host;
   const T* tabs = nullptr;  // host copy (fused2/3: kernarg tables) or device buffer (fused5)
   T *x, *r, *pa, *pb, *y, *yb, *zb, *cb;
-  // Tiled storage (cfg.latdT[17] != 0): the iteration runs on tiled copies
+  // Tiled storage (a tiled descriptor cfg.latdT): the iteration runs on tiled copies
   // xt, rt, pat, pbt, yt (allocated zeroed by the caller: the padding stays
   // zero); r and x are imported after each prologue and x is exported after
   // every iterate() / profile().  wx .. wy: the buffers the loop works on.
@@ -674,12 +673,10 @@ struct CGRuntime final : LoopBase {
     const int cur = (k % 2 == 0) ? kRR0 : kRR1, nxt = cur == kRR0 ? kRR1 : kRR0;
     T* pold = (k % 2 == 0) ? wpa : wpb;
     T* pnew = (k % 2 == 0) ? wpb : wpa;
-    // mode word: CG | x mode (bits 4-5) | odd-tile x mode + 1 (6-7, 0: not
-    // staggered) | segments (8-15) | saved-alpha slot parity to write (16)
-    // and to read (17)
-    const int m1 = stagger ? cur_m1 + 1 : 0;
-    const int word = 1 | (xm << 4) | (m1 << 6) | (cfg.nseg << 8) | static_cast<int>((k & 1) << 16) |
-                     static_cast<int>(((k + 1) & 1) << 17);
+    // the saved alpha is written to the slot of this iteration's parity and
+    // read from the other
+    const int word = fused_mode_pack(kFusedCG, cfg.nseg, xm, stagger ? cur_m1 : -1,
+                                     static_cast<int>(k & 1), static_cast<int>((k + 1) & 1));
     return apply(word, cfg.affine, wlatd, cfg.nq, cfg.wts.data(), cfg.qpts.data(), u_vector(),
                  pold, pnew, wx, wy, yb, zb, cb, xv, kc, tabs, cfg.kappa, scal, partials,
                  first ? -1 : cur, first ? -1 : nxt, xlag ? nxt : -1, xlag ? kPAP : -1, cfg.nty,
@@ -805,10 +802,9 @@ struct CGRuntime final : LoopBase {
   // on cs with a 1-rank RCCL communicator: grouped self send/recv of n
   // doubles (buf[0, n) -> buf[n, 2n)), the last tile row and column, the
   // reverse send/recv; concurrently st runs the interior tile rectangle.
-  // out (ms, medians over reps): 0 chain alone, 1 interior alone, 2 chain
-  // done and 3 interior done measured from the common fork, 4 one exchange
-  // alone.  The CG state is clobbered: the caller restarts CG afterwards.
-  int overlap_probe(int64_t n, double* buf, int reps, double* out) {
+  // *out: medians over reps (BdxRtOverlapProbe).  The CG state is clobbered:
+  // the caller restarts CG afterwards.
+  int overlap_probe(int64_t n, double* buf, int reps, BdxRtOverlapProbe* out) {
     if (nranks != 1 || cfg.nty < 2 || cfg.ntz < 2 || n <= 0 || reps <= 0)
       return static_cast<int>(hipErrorInvalidValue);
     ncclUniqueId id;
@@ -849,7 +845,8 @@ struct CGRuntime final : LoopBase {
     if (!rc) rc = launch_op(0, true, false, kXSingle, ra, st);
     if (rc) return rc;
     BDX_CHECK(hipDeviceSynchronize());
-    std::vector<double> v[6];
+    std::vector<double> chain_alone, interior_alone, chain_done, interior_done, exchange_alone,
+        fwd_exchange_done;
     bdx::Watchdog::Busy busy(t.watchdog());
     for (int it = 0; it < reps; ++it) {
       // alone: the chain, the interior, one exchange (each drained before the next)
@@ -861,13 +858,13 @@ struct CGRuntime final : LoopBase {
       if ((rc = launch_op(0, true, false, kXSingle, ra, st))) return rc;
       BDX_CHECK(hipEventRecord(e[3], st));
       BDX_CHECK(hipDeviceSynchronize());
-      v[0].push_back(ms(0, 1));
-      v[1].push_back(ms(2, 3));
+      chain_alone.push_back(ms(0, 1));
+      interior_alone.push_back(ms(2, 3));
       BDX_CHECK(hipEventRecord(e[0], cs));
       if ((rc = xchg(cs))) return rc;
       BDX_CHECK(hipEventRecord(e[1], cs));
       BDX_CHECK(hipDeviceSynchronize());
-      v[4].push_back(ms(0, 1));
+      exchange_alone.push_back(ms(0, 1));
       // together, enqueued in the runtime's order: fork, cs chain, st interior
       BDX_CHECK(hipEventRecord(e[0], st));
       BDX_CHECK(hipStreamWaitEvent(cs, e[0], 0));
@@ -876,14 +873,20 @@ struct CGRuntime final : LoopBase {
       if ((rc = launch_op(0, true, false, kXSingle, ra, st))) return rc;
       BDX_CHECK(hipEventRecord(e[2], st));
       BDX_CHECK(hipDeviceSynchronize());
-      v[2].push_back(ms(0, 1));
-      v[3].push_back(ms(0, 2));
-      v[5].push_back(ms(0, 4));
+      chain_done.push_back(ms(0, 1));
+      interior_done.push_back(ms(0, 2));
+      fwd_exchange_done.push_back(ms(0, 4));
     }
-    for (int i = 0; i < 6; ++i) {
-      std::sort(v[i].begin(), v[i].end());
-      out[i] = v[i][v[i].size() / 2];
-    }
+    auto median = [](std::vector<double>& v) {
+      std::sort(v.begin(), v.end());
+      return v[v.size() / 2];
+    };
+    out->chain_alone_ms = median(chain_alone);
+    out->interior_alone_ms = median(interior_alone);
+    out->chain_done_ms = median(chain_done);
+    out->interior_done_ms = median(interior_done);
+    out->exchange_alone_ms = median(exchange_alone);
+    out->fwd_exchange_done_ms = median(fwd_exchange_done);
     return 0;
   }
 };
@@ -897,7 +900,7 @@ struct CGRuntime final : LoopBase {
 // scatter_fwd_end / bcells schedule (src/laplacian.hpp:281-349), without its
 // host syncs and with the boundary cells off the critical path.
 struct DofConfig {
-  int64_t latd[21];
+  int64_t latd[kLatticeWords];
   int P, nq, geom, n_inner, n_outer, nb_inner, nb_outer;
   int64_t nvec;
   double kappa;
@@ -1020,36 +1023,28 @@ struct DofCGRuntime final : LoopBase {
   }
 };
 
-// iparams of the fused kind: version, affine, P, nq, nblocks, nty, ntz, sy,
-// sz, use_graph, overlap, nseg (nblocks = nty * ntz * nseg p.Ap partials)
 template <typename T>
-LoopBase* create(const int64_t* latd, const int64_t* own, const int* iparams, double kappa,
-                 const double* wts, const double* qpts, const void* tabs, void* const* ptrs,
-                 const int64_t* halo_sizes, const int64_t* face_cnt, const int64_t* ghost_cnt,
-                 int transport, int nranks, int rank, int64_t group_id, hipStream_t st,
-                 const int64_t* latd_tiled, void* const* tptrs) {
+LoopBase* create(const BdxRtFusedSetup& s, hipStream_t st) {
   auto rt = std::make_unique<CGRuntime<T>>();
   rt->esize = sizeof(T);
   RtConfig& c = rt->cfg;
-  std::memcpy(c.latd, latd, sizeof(c.latd));
-  std::memset(c.latdT, 0, sizeof(c.latdT));
-  if (latd_tiled && latd_tiled[17] && tptrs) std::memcpy(c.latdT, latd_tiled, sizeof(c.latdT));
-  std::memcpy(c.own, own, sizeof(c.own));
-  c.version = iparams[0];
-  c.affine = iparams[1];
-  c.P = iparams[2];
-  c.nq = iparams[3];
-  c.nblocks = iparams[4];
-  c.nty = iparams[5];
-  c.ntz = iparams[6];
-  c.sy = iparams[7];
-  c.sz = iparams[8];
-  rt->use_graph = iparams[9] != 0;
-  const bool overlap = iparams[10] != 0;
-  c.nseg = iparams[11] > 0 ? iparams[11] : 1;
-  c.kappa = kappa;
-  c.wts.assign(wts, wts + c.nq);
-  c.qpts.assign(qpts, qpts + c.nq);
+  std::memcpy(c.latd, s.latd, sizeof(c.latd));
+  std::memcpy(c.latdT, s.latd_tiled, sizeof(c.latdT));
+  std::memcpy(c.own, s.own, sizeof(c.own));
+  c.version = s.version;
+  c.affine = s.affine;
+  c.P = s.P;
+  c.nq = s.nq;
+  c.nblocks = s.nblocks;
+  c.nty = s.nty;
+  c.ntz = s.ntz;
+  c.sy = s.sy;
+  c.sz = s.sz;
+  rt->use_graph = s.use_graph != 0;
+  c.nseg = s.nseg > 0 ? s.nseg : 1;
+  c.kappa = s.kappa;
+  c.wts.assign(s.wts, s.wts + c.nq);
+  c.qpts.assign(s.qpts, s.qpts + c.nq);
   rt->apply = apply_fn<T>(c.version, c.P);
   // paired lagged x update (fused5 only; BDX_XPAIR=0 folds one term per
   // iteration).  Paired on every tile at once, every other iteration carries
@@ -1062,41 +1057,34 @@ LoopBase* create(const int64_t* latd, const int64_t* own, const int* iparams, do
     const char* e = std::getenv("BDX_XPAIR");
     rt->xpair = c.version == 5 && !(e && e[0] == '0');
   }
-  if (!rt->apply || !tabs) return nullptr;
+  if (!rt->apply || !bdx_rt_fused_setup_ok(s)) return nullptr;
   if (c.version == 5) {
-    rt->tabs = static_cast<const T*>(tabs);  // the operator's device table buffer
+    rt->tabs = static_cast<const T*>(s.tabs);  // the operator's device table buffer
   } else {
-    const T* tb = static_cast<const T*>(tabs);
+    const T* tb = static_cast<const T*>(s.tabs);
     rt->tabs_host.assign(tb, tb + kFusedTabMax);
     rt->tabs = rt->tabs_host.data();
   }
-  int i = 0;
-  rt->x = static_cast<T*>(ptrs[i++]);
-  rt->r = static_cast<T*>(ptrs[i++]);
-  rt->pa = static_cast<T*>(ptrs[i++]);
-  rt->pb = static_cast<T*>(ptrs[i++]);
-  rt->y = static_cast<T*>(ptrs[i++]);
-  rt->yb = static_cast<T*>(ptrs[i++]);
-  rt->zb = static_cast<T*>(ptrs[i++]);
-  rt->cb = static_cast<T*>(ptrs[i++]);
-  rt->xv = static_cast<const T*>(ptrs[i++]);
-  rt->scal = static_cast<double*>(ptrs[i++]);
-  rt->partials = static_cast<double*>(ptrs[i++]);
-  rt->upart = static_cast<double*>(ptrs[i++]);
-  void* const* hptrs = ptrs + i;  // hbuf_a, hbuf_b, face_boxes, ghost_boxes
-  i += 4;
-  rt->kc = static_cast<const T*>(ptrs[i++]);
-  rt->is_tiled = c.latdT[17] != 0;
+  rt->x = static_cast<T*>(s.x);
+  rt->r = static_cast<T*>(s.r);
+  rt->pa = static_cast<T*>(s.p_a);
+  rt->pb = static_cast<T*>(s.p_b);
+  rt->y = static_cast<T*>(s.y);
+  rt->yb = static_cast<T*>(s.yb);
+  rt->zb = static_cast<T*>(s.zb);
+  rt->cb = static_cast<T*>(s.cb);
+  rt->xv = static_cast<const T*>(s.xv);
+  rt->kc = static_cast<const T*>(s.kc);
+  rt->scal = s.scal;
+  rt->partials = s.partials;
+  rt->upart = s.upart;
+  rt->is_tiled = BdxLattice::from(c.latdT).tsy != 0;
   if (rt->is_tiled) {
-    // only the x-march kernels whose tile is the storage tile address it
-    if ((c.version != 3 && c.version != 5) || c.latdT[17] != c.sy || c.latdT[18] != c.sz)
-      return nullptr;
-    rt->xt = static_cast<T*>(tptrs[0]);
-    rt->rt_ = static_cast<T*>(tptrs[1]);
-    rt->pat = static_cast<T*>(tptrs[2]);
-    rt->pbt = static_cast<T*>(tptrs[3]);
-    rt->yt = static_cast<T*>(tptrs[4]);
-    if (!rt->xt || !rt->rt_ || !rt->pat || !rt->pbt || !rt->yt) return nullptr;
+    rt->xt = static_cast<T*>(s.xt);
+    rt->rt_ = static_cast<T*>(s.rt);
+    rt->pat = static_cast<T*>(s.pat);
+    rt->pbt = static_cast<T*>(s.pbt);
+    rt->yt = static_cast<T*>(s.yt);
   }
   // staggered pairing needs the flush's per-tile colours (tiled storage);
   // BDX_XSTAGGER=0 pairs every tile on the same iterations
@@ -1110,14 +1098,12 @@ LoopBase* create(const int64_t* latd, const int64_t* own, const int* iparams, do
   rt->wpb = rt->is_tiled ? rt->pbt : rt->pb;
   rt->wy = rt->is_tiled ? rt->yt : rt->y;
   rt->wlatd = rt->is_tiled ? c.latdT : c.latd;
-  if (rt->init_common(st, hptrs, halo_sizes, face_cnt, ghost_cnt, transport, nranks, rank,
-                      group_id))
-    return nullptr;
+  if (rt->init_common(st, s.halo)) return nullptr;
   // overlapped schedule: x whole, so only the last tile row (y ghost plane)
   // and the last tile column (z ghost plane) touch ghosts
   const BdxLattice L = BdxLattice::from(c.latd);
   const int g1 = static_cast<int>(L.gh[1]), g2 = static_cast<int>(L.gh[2]);
-  if (overlap && rt->halo && L.gh[0] == 0 && (g1 || g2)) {
+  if (s.overlap && rt->halo && L.gh[0] == 0 && (g1 || g2)) {
     const int iy = c.nty - g1, iz = c.ntz - g2;  // interior tile extents
     const int ra[4] = {0, iy, 0, iz};
     const int r1[4] = {iy, c.nty, 0, c.ntz}, r2[4] = {0, iy, iz, c.ntz};
@@ -1130,63 +1116,50 @@ LoopBase* create(const int64_t* latd, const int64_t* own, const int* iparams, do
   return rt.release();
 }
 
-// iparams of the dofmap kind: P, nq, geom, n_inner, n_outer, use_graph,
-// overlap; ptrs: x, r, p_a, p_b, y, scal, partials, upart, hbuf_a, hbuf_b,
-// face_boxes, ghost_boxes, tab, inner, outer, cdofs, cverts, coords, flags, G,
-// kc (G / kc may be null)
 template <typename T>
-LoopBase* create_dofmap(const int64_t* latd, const int* iparams, int64_t nvec, double kappa,
-                        void* const* ptrs, const int64_t* halo_sizes, const int64_t* face_cnt,
-                        const int64_t* ghost_cnt, int transport, int nranks, int rank,
-                        int64_t group_id, hipStream_t st) {
+LoopBase* create_dofmap(const BdxRtDofmapSetup& s, hipStream_t st) {
   auto rt = std::make_unique<DofCGRuntime<T>>();
   rt->esize = sizeof(T);
   DofConfig& c = rt->cfg;
-  std::memcpy(c.latd, latd, sizeof(c.latd));
-  c.P = iparams[0];
-  c.nq = iparams[1];
-  c.geom = iparams[2];
-  c.n_inner = iparams[3];
-  c.n_outer = iparams[4];
-  rt->use_graph = iparams[5] != 0;
-  const bool overlap = iparams[6] != 0;
-  c.nvec = nvec;
-  c.kappa = kappa;
+  std::memcpy(c.latd, s.latd, sizeof(c.latd));
+  c.P = s.P;
+  c.nq = s.nq;
+  c.geom = s.geom;
+  c.n_inner = s.n_inner;
+  c.n_outer = s.n_outer;
+  rt->use_graph = s.use_graph != 0;
+  c.nvec = s.nvec;
+  c.kappa = s.kappa;
   c.nb_inner = bdx_dofmap_nblocks(c.nq, c.n_inner);
   c.nb_outer = bdx_dofmap_nblocks(c.nq, c.n_outer);
   if (c.nb_inner < 0 || c.nb_outer < 0 || c.nb_inner + c.nb_outer > bdx_hip_partials_size())
     return nullptr;
-  int i = 0;
-  rt->x = static_cast<T*>(ptrs[i++]);
-  rt->r = static_cast<T*>(ptrs[i++]);
-  rt->pa = static_cast<T*>(ptrs[i++]);
-  rt->pb = static_cast<T*>(ptrs[i++]);
-  rt->y = static_cast<T*>(ptrs[i++]);
-  rt->scal = static_cast<double*>(ptrs[i++]);
-  rt->partials = static_cast<double*>(ptrs[i++]);
-  rt->upart = static_cast<double*>(ptrs[i++]);
-  void* const* hptrs = ptrs + i;
-  i += 4;
-  rt->tab = static_cast<const T*>(ptrs[i++]);
-  rt->inner = static_cast<const int*>(ptrs[i++]);
-  rt->outer = static_cast<const int*>(ptrs[i++]);
-  rt->cdofs = static_cast<const int*>(ptrs[i++]);
-  rt->cverts = static_cast<const int*>(ptrs[i++]);
-  rt->coords = static_cast<const T*>(ptrs[i++]);
-  rt->flags = static_cast<const unsigned char*>(ptrs[i++]);
-  rt->G = static_cast<const T*>(ptrs[i++]);
-  rt->kc = static_cast<const T*>(ptrs[i++]);
-  if (!rt->tab || !rt->cdofs || !rt->flags || (c.geom == kGeomStored && !rt->G)) return nullptr;
-  if (hipMalloc(&rt->y2, static_cast<size_t>(nvec) * sizeof(T)) != hipSuccess ||
-      hipMemset(rt->y2, 0, static_cast<size_t>(nvec) * sizeof(T)) != hipSuccess) {
+  if (!bdx_rt_dofmap_setup_ok(s)) return nullptr;
+  rt->x = static_cast<T*>(s.x);
+  rt->r = static_cast<T*>(s.r);
+  rt->pa = static_cast<T*>(s.p_a);
+  rt->pb = static_cast<T*>(s.p_b);
+  rt->y = static_cast<T*>(s.y);
+  rt->scal = s.scal;
+  rt->partials = s.partials;
+  rt->upart = s.upart;
+  rt->tab = static_cast<const T*>(s.tab);
+  rt->inner = s.inner;
+  rt->outer = s.outer;
+  rt->cdofs = s.cdofs;
+  rt->cverts = s.cverts;
+  rt->coords = static_cast<const T*>(s.coords);
+  rt->flags = s.flags;
+  rt->G = static_cast<const T*>(s.G);
+  rt->kc = static_cast<const T*>(s.kc);
+  if (hipMalloc(&rt->y2, static_cast<size_t>(c.nvec) * sizeof(T)) != hipSuccess ||
+      hipMemset(rt->y2, 0, static_cast<size_t>(c.nvec) * sizeof(T)) != hipSuccess) {
     (void)hipGetLastError();
     return nullptr;
   }
   rt->wlatd = c.latd;
-  if (rt->init_common(st, hptrs, halo_sizes, face_cnt, ghost_cnt, transport, nranks, rank,
-                      group_id))
-    return nullptr;
-  rt->split = overlap && rt->halo && c.n_outer > 0;
+  if (rt->init_common(st, s.halo)) return nullptr;
+  rt->split = s.overlap && rt->halo && c.n_outer > 0;
   if (rt->split && rt->make_interior_stream()) return nullptr;
   return rt.release();
 }
@@ -1249,53 +1222,29 @@ int bdx_rt_rccl_selftest(double* buf, int n, hipStream_t st) {
   return rc;
 }
 
-// latd_tiled / tptrs (may be null): the tiled-storage descriptor and the
-// runtime's tiled x, r, p_a, p_b, y buffers (zero-initialised by the caller).
-void* bdx_rt_create(int is_f64, const int64_t* latd, const int64_t* own, const int* iparams,
-                    double kappa, const double* wts, const double* qpts, const void* tabs,
-                    void* const* ptrs, const int64_t* halo_sizes, const int64_t* face_cnt,
-                    const int64_t* ghost_cnt, int transport, int nranks, int rank,
-                    int64_t group_id, hipStream_t st, const int64_t* latd_tiled,
-                    void* const* tptrs) {
-  if (is_f64)
-    return create<double>(latd, own, iparams, kappa, wts, qpts, tabs, ptrs, halo_sizes,
-                          face_cnt, ghost_cnt, transport, nranks, rank, group_id, st, latd_tiled,
-                          tptrs);
-  return create<float>(latd, own, iparams, kappa, wts, qpts, tabs, ptrs, halo_sizes, face_cnt,
-                       ghost_cnt, transport, nranks, rank, group_id, st, latd_tiled, tptrs);
+void* bdx_rt_create(const BdxRtFusedSetup* setup, hipStream_t st) {
+  return setup->is_f64 ? create<double>(*setup, st) : create<float>(*setup, st);
 }
 
-// The dofmap data model's CG loop (see create_dofmap for the arguments).
-void* bdx_rt_create_dofmap(int is_f64, const int64_t* latd, const int* iparams, int64_t nvec,
-                           double kappa, void* const* ptrs, const int64_t* halo_sizes,
-                           const int64_t* face_cnt, const int64_t* ghost_cnt, int transport,
-                           int nranks, int rank, int64_t group_id, hipStream_t st) {
-  if (is_f64)
-    return create_dofmap<double>(latd, iparams, nvec, kappa, ptrs, halo_sizes, face_cnt,
-                                 ghost_cnt, transport, nranks, rank, group_id, st);
-  return create_dofmap<float>(latd, iparams, nvec, kappa, ptrs, halo_sizes, face_cnt, ghost_cnt,
-                              transport, nranks, rank, group_id, st);
+void* bdx_rt_create_dofmap(const BdxRtDofmapSetup* setup, hipStream_t st) {
+  return setup->is_f64 ? create_dofmap<double>(*setup, st) : create_dofmap<float>(*setup, st);
 }
 
-// Comm stream priority: out[0] least, out[1] greatest (device range),
-// out[2] the priority the comm stream runs at.
-int bdx_rt_comm_priority(void* h, int* out) {
+int bdx_rt_comm_priority(void* h, BdxRtCommPriority* out) {
   return with_rt(h, [&](LoopBase* rt) {
-    out[0] = rt->prio_least;
-    out[1] = rt->prio_greatest;
-    out[2] = rt->prio_cs;
+    *out = {rt->prio_least, rt->prio_greatest, rt->prio_cs};
     return 0;
   });
 }
 
-// Transport pre-flight (see LoopBase::preflight); out[2].
-int bdx_rt_preflight(void* h, double timeout_s, double* out) {
+// Transport pre-flight (see LoopBase::preflight).
+int bdx_rt_preflight(void* h, double timeout_s, BdxRtPreflight* out) {
   return with_rt(h, [&](LoopBase* rt) { return rt->preflight(timeout_s, out); });
 }
 
 // Comm/compute overlap probe on one GPU (see CGRuntime::overlap_probe;
-// fused operators only); buf: 2 n doubles; out[6].
-int bdx_rt_overlap_probe(void* h, int64_t n, double* buf, int reps, double* out) {
+// fused operators only); buf: 2 n doubles.
+int bdx_rt_overlap_probe(void* h, int64_t n, double* buf, int reps, BdxRtOverlapProbe* out) {
   return with_rt(h, [&](LoopBase* rt) -> int {
     if (auto* f = dynamic_cast<CGRuntime<double>*>(rt)) return f->overlap_probe(n, buf, reps, out);
     if (auto* f = dynamic_cast<CGRuntime<float>*>(rt)) return f->overlap_probe(n, buf, reps, out);
@@ -1402,21 +1351,9 @@ int bdx_rt_wait(void* h) {
   return with_rt(h, [](LoopBase* rt) { return rt->tr->wait(rt->ev_out); });
 }
 
-// n eager CG iterations with hipEvent phase timers; out (13 doubles, mean ms):
-//   0 forward halo (comm stream: pack, exchange, unpack)
-//   1 operator, interior tiles / cells (serial schedule: the first launch)
-//   2 boundary work: split: ghost-touching tiles / cells (+ ghost fold)
-//     after the forward halo; serial: what follows the first launch
-//   3 reverse halo (pack, exchange; serial: + unpack-add)
-//   4 interior done -> comm stream joined, received sums added
-//   5 reduce + all-reduce(p.Ap)
-//   6 r update + r.r
-//   7 all-reduce(r.r)
-//   8 whole iteration
-//   9..12 end of the forward halo / boundary work / reverse halo / interior
-//         work, measured from the iteration start (overlap evidence)
-int bdx_rt_profile(void* h, long n, double* out, int nout) {
-  return with_rt(h, [&](LoopBase* rt) { return rt->profile(n, out, nout); });
+// n eager CG iterations with hipEvent phase timers (BdxRtPhases: mean ms).
+int bdx_rt_profile(void* h, long n, BdxRtPhases* out) {
+  return with_rt(h, [&](LoopBase* rt) { return rt->profile(n, out); });
 }
 
 // it (iterations done) and whether steady-state graphs are in use.

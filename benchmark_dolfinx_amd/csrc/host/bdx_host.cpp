@@ -838,6 +838,9 @@ extern "C" {
 
 int bdx_host_version() { return 1; }
 
+int bdx_cpu_rt_fused_setup_ok(const BdxRtFusedSetup* s) { return bdx_rt_fused_setup_ok(*s); }
+int bdx_cpu_rt_dofmap_setup_ok(const BdxRtDofmapSetup* s) { return bdx_rt_dofmap_setup_ok(*s); }
+
 #define BDX_HOST_API(T, SUF)                                                  \
   void bdx_cpu_stiffness_##SUF BDX_P_CPU_STIFFNESS(T) {                       \
     StiffArgs<T> a;                                                           \

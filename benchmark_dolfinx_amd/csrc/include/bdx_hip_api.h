@@ -13,6 +13,8 @@
 #pragma once
 #include <cstdint>
 
+#include "bdx_rt_setup.h"  // the CG runtimes' setup and result records
+
 // as in hip/hip_runtime_api.h (a legal re-declaration): readable without HIP
 typedef struct ihipStream_t* hipStream_t;
 
@@ -152,8 +154,7 @@ BDX_TWINS(int, bdx_fused3_tables, BDX_P_FUSED3_TABLES)
 BDX_FUSED_DEGREES(BDX_DECL_FUSED_V1, double, f64)
 BDX_FUSED_DEGREES(BDX_DECL_FUSED_V1, float, f32)
 // The fused2 / fused3 / fused5 operator apply (the one 28-parameter list).
-// mode: kind (action / CG) | x-mode bits (fused5) | segments << 8 (0 -> 1);
-// rect: host {ty0, ty1, tz0, tz1} restricting the launch to a tile rectangle
+// mode: the word of fused_mode_pack below; rect: host {ty0, ty1, tz0, tz1} restricting the launch to a tile rectangle
 // (null: every tile).  tabs: host memory for fused2 / fused3 (bdx_fused_tables,
 // bdx_fused3_tables), the operator's device table buffer for fused5.
 #define BDX_P_FUSED_APPLY(T) (int mode, int affine_ok, const int64_t* latd, int nq, const double* wts, \
@@ -168,6 +169,30 @@ BDX_FUSED_DEGREES(BDX_DECL_FUSED_APPLY, 3, double, f64)
 BDX_FUSED_DEGREES(BDX_DECL_FUSED_APPLY, 3, float, f32)
 BDX_FUSED5_DEGREES(BDX_DECL_FUSED_APPLY, 5, double, f64)
 BDX_FUSED5_DEGREES(BDX_DECL_FUSED_APPLY, 5, float, f32)
+}  // extern "C"
+// The mode word of BDX_P_FUSED_APPLY: kind (kFusedAction / kFusedCG, bits 0-3)
+// | x mode of the lagged x update (kXSingle / kXSave / kXPair, bits 4-5) | the
+// odd tiles' x mode + 1 (bits 6-7; 0, xmode1 = -1: not staggered) | x segments
+// (bits 8-15, 0 -> 1) | parity of the saved-alpha slot to write (bit 16) and to
+// read (bit 17).  Only fused5 has x modes; Python packs kind and segments
+// (models/fused.py, with ops/hip_api.py: CONSTANTS).
+enum { kFusedAction = 0, kFusedCG = 1 };
+constexpr int kFusedModeSegShift = 8;
+constexpr int fused_mode_pack(int kind, int nseg, int xmode = 0, int xmode1 = -1, int xsave_w = 0,
+                              int xsave_r = 0) {
+  return kind | (xmode << 4) | ((xmode1 + 1) << 6) | (nseg << kFusedModeSegShift) | (xsave_w << 16) |
+         (xsave_r << 17);
+}
+constexpr int fused_mode_kind(int mode) { return mode & 0xf; }
+// the kind as a kernel without x modes reads it: a word that carries one is
+// no CG launch
+constexpr int fused_mode_kind_nox(int mode) { return mode & 0xff; }
+constexpr int fused_mode_xmode(int mode) { return (mode >> 4) & 3; }
+constexpr int fused_mode_xmode1(int mode) { return ((mode >> 6) & 3) - 1; }
+constexpr int fused_mode_nseg(int mode) { return (mode >> kFusedModeSegShift) & 0xff; }
+constexpr int fused_mode_xsave_w(int mode) { return (mode >> 16) & 1; }
+constexpr int fused_mode_xsave_r(int mode) { return (mode >> 17) & 1; }
+extern "C" {
 // x segments (fused_choose_segments) of a fused2 / fused3 CG launch of `tiles`
 // tiles of ncx cell layers on this device.  Returns the count; no stream.
 #define BDX_DECL_FUSED_SEGMENTS(PP, V, SUF) \
@@ -329,27 +354,17 @@ int bdx_rt_nccl_unique_id(void* out128);
 // Hardware self-test of the RCCL transport on one GPU; buf: 3 n + 2 doubles.
 int bdx_rt_rccl_selftest(double* buf, int n, hipStream_t st);
 // The fused structured CG loop; returns the runtime handle h of the calls
-// below (null when refused).  latd_tiled / tptrs (may be null): the
-// tiled-storage descriptor and the runtime's tiled x, r, p_a, p_b, y buffers.
-void* bdx_rt_create(int is_f64, const int64_t* latd, const int64_t* own, const int* iparams,
-                    double kappa, const double* wts, const double* qpts, const void* tabs,
-                    void* const* ptrs, const int64_t* halo_sizes, const int64_t* face_cnt,
-                    const int64_t* ghost_cnt, int transport, int nranks, int rank,
-                    int64_t group_id, hipStream_t st, const int64_t* latd_tiled,
-                    void* const* tptrs);
+// below (null when refused).  The records: bdx_rt_setup.h.
+void* bdx_rt_create(const BdxRtFusedSetup* setup, hipStream_t st);
 // The dofmap data model's CG loop (handle as above).
-void* bdx_rt_create_dofmap(int is_f64, const int64_t* latd, const int* iparams, int64_t nvec,
-                           double kappa, void* const* ptrs, const int64_t* halo_sizes,
-                           const int64_t* face_cnt, const int64_t* ghost_cnt, int transport,
-                           int nranks, int rank, int64_t group_id, hipStream_t st);
-// Comm stream priority: out[0] least, out[1] greatest (device range),
-// out[2] the priority the comm stream runs at.
-int bdx_rt_comm_priority(void* h, int* out);
-// Transport pre-flight; out[2].
-int bdx_rt_preflight(void* h, double timeout_s, double* out);
+void* bdx_rt_create_dofmap(const BdxRtDofmapSetup* setup, hipStream_t st);
+// Priority of the comm stream and the device's range.
+int bdx_rt_comm_priority(void* h, BdxRtCommPriority* out);
+// Transport pre-flight.
+int bdx_rt_preflight(void* h, double timeout_s, BdxRtPreflight* out);
 // Comm/compute overlap probe on one GPU (fused operators only); buf: 2 n
-// doubles; out[6].
-int bdx_rt_overlap_probe(void* h, int64_t n, double* buf, int reps, double* out);
+// doubles.
+int bdx_rt_overlap_probe(void* h, int64_t n, double* buf, int reps, BdxRtOverlapProbe* out);
 // 1 if the loop runs on the tiled storage layout.
 int bdx_rt_tiled(void* h);
 // Open the runtime's RCCL communicator (collective over the ranks).  0 on
@@ -372,8 +387,8 @@ int bdx_rt_iterate(void* h, long n);
 int bdx_rt_iterate_timed(void* h, long n, float* step_ms);
 // Host wait for everything iterate() queued, bounded by the RCCL deadline.
 int bdx_rt_wait(void* h);
-// n eager CG iterations with hipEvent phase timers; out: 13 doubles, mean ms.
-int bdx_rt_profile(void* h, long n, double* out, int nout);
+// n eager CG iterations with hipEvent phase timers; out: mean ms per phase.
+int bdx_rt_profile(void* h, long n, BdxRtPhases* out);
 // it (iterations done) and whether steady-state graphs are in use.
 int bdx_rt_state(void* h, long* it, int* graphs);
 // Destroy a runtime handle.

@@ -8,6 +8,8 @@
 #pragma once
 #include <cstdint>
 
+#include "bdx_rt_setup.h"
+
 #define BDX_HOST_TWINS(R, NAME, PARAMS) \
   R NAME##_f64 PARAMS(double);          \
   R NAME##_f32 PARAMS(float);
@@ -17,6 +19,11 @@ extern "C" {
 // -------------------------------------------------------------- bdx_host.cpp
 // ABI version of the host library.
 int bdx_host_version();
+// The CG runtimes' own checks of a setup record (bdx_rt_setup.h), as
+// bdx_rt_create / bdx_rt_create_dofmap make them: 1 = accepted.  Nothing the
+// record points to is read.
+int bdx_cpu_rt_fused_setup_ok(const BdxRtFusedSetup* s);
+int bdx_cpu_rt_dofmap_setup_ok(const BdxRtDofmapSetup* s);
 // y += A u over the cells [lo, hi) of the local lattice (geometry on the fly).
 #define BDX_P_CPU_STIFFNESS(T) (const int64_t* latd, int nq, const T* phi0, const T* dphi1, const T* wts, \
   const T* qpts, const T* nodes, int identity, const T* xv, T kappa, const T* kc, const T* u, T* y, \

@@ -31,6 +31,8 @@
 #define BDX_HD inline
 #endif
 
+constexpr int kLatticeWords = 21;  // int64 words of the packed descriptor
+
 struct BdxLattice {
   int64_t n[3];
   int64_t L[3];
@@ -86,3 +88,5 @@ struct BdxLattice {
     return ((a * (n[1] + 1) + b) * (n[2] + 1) + c);
   }
 };
+// the struct is the packed descriptor, word for word (ops/hip_api.py: Lattice)
+static_assert(sizeof(BdxLattice) == kLatticeWords * 8, "BdxLattice is not the packed descriptor");

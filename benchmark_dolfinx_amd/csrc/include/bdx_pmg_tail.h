@@ -8,6 +8,7 @@
 //   [31]     number of Chebyshev steps   [32] word offset of their (a, b)
 // r and z of the first level are call arguments (the caller's vectors).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "bdx_mg_bodies.h"
@@ -29,6 +30,33 @@ enum {
   kTailNcoef,
   kTailCoef
 };
+
+// One level's words by name: what ops/kernels.py: PmgTail fills (through the
+// mirror ops/hip_api.py: TailLevelWords).  Pointers travel as words.
+struct BdxTailLevelWords {
+  BdxLattice lat;
+  int64_t S, dinv, bc, r, z, d, y;
+  int64_t cidx, cw, fpos;
+  int64_t ncoef, coef;
+  int64_t pad[kTailWords - kTailCoef - 1];
+};
+static_assert(sizeof(BdxTailLevelWords) == kTailWords * 8, "a level is kTailWords words");
+#define BDX_TAIL_SLOT(FIELD, SLOT)                                      \
+  static_assert(offsetof(BdxTailLevelWords, FIELD) == (SLOT) * 8, \
+                #FIELD " is not at word " #SLOT)
+BDX_TAIL_SLOT(S, kTailS);
+BDX_TAIL_SLOT(dinv, kTailDinv);
+BDX_TAIL_SLOT(bc, kTailBc);
+BDX_TAIL_SLOT(r, kTailR);
+BDX_TAIL_SLOT(z, kTailZ);
+BDX_TAIL_SLOT(d, kTailD);
+BDX_TAIL_SLOT(y, kTailY);
+BDX_TAIL_SLOT(cidx, kTailCidx);
+BDX_TAIL_SLOT(cw, kTailCw);
+BDX_TAIL_SLOT(fpos, kTailFpos);
+BDX_TAIL_SLOT(ncoef, kTailNcoef);
+BDX_TAIL_SLOT(coef, kTailCoef);
+#undef BDX_TAIL_SLOT
 
 // A level the tail can run: lattice layout, degree 1, no ghost planes (one
 // rank), at most kTailMaxNodes nodes.

@@ -30,6 +30,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from ..ops.hip_api import Lattice
+
 
 def compute_mesh_size(ndofs_global: int, degree: int) -> tuple[int, int, int]:
     """Choose (nx, ny, nz) so that prod(n_d*P+1) is closest to ndofs_global.
@@ -182,12 +184,14 @@ class LocalLattice:
     def as_int64(self, tile: tuple[int, int] | None = None) -> np.ndarray:
         """Packed descriptor passed to native code (layout: csrc/include/bdx_lattice.h).
         `tile` = (tsy, tsz) node sizes selects the tiled storage layout."""
-        tl = [0, 0, 0, 0]
+        w = {"n": self.n, "L": self.L, "g0": self.g0, "N": self.N, "gh": self.gh,
+             "P": self.degree, "ld": self.ld, "tsy": 0, "tsz": 0, "tntz": 0, "tcol": 0}
         if tile is not None:
             tsy, tsz = tile
-            tl = [tsy, tsz, (self.L[2] - 1) // tsz + 1, self.L[0] * tsy * tsz]
-        return np.array(list(self.n) + list(self.L) + list(self.g0) + list(self.N)
-                        + list(self.gh) + [self.degree, self.ld] + tl, dtype=np.int64)
+            w.update(tsy=tsy, tsz=tsz, tntz=(self.L[2] - 1) // tsz + 1, tcol=self.L[0] * tsy * tsz)
+        # in the order of the struct's fields (ops/hip_api.py: Lattice)
+        return np.array([v for name, _ in Lattice._fields_ for v in np.atleast_1d(w[name])],
+                        dtype=np.int64)
 
     def tiled_size(self, tsy: int, tsz: int) -> int:
         """Elements of a vector in the tiled storage layout (tiles of tsy x tsz

@@ -29,9 +29,12 @@ import numpy as np
 import torch
 
 from ..ops import native
+from ..ops.hip_api import CONSTANTS
 from ..ops.kernels import _check, _stream
 from ..ops.native import ptr
 from ..utils.timing import timed
+
+MODE_SEG_SHIFT = CONSTANTS["kFusedModeSegShift"]  # the x segments' bits of the apply's mode word
 
 
 def fused_supported(pb, version: int = 1) -> bool:
@@ -200,7 +203,7 @@ class FusedLaplacianGPU:
                 xa_num=-1, xa_den=-1, finalize=True):
         pb, t = self.pb, self.t
         if self.version >= 2:
-            _check(self._apply2(mode | (self.nseg << 8), self.affine_code, ptr(pb.latd), t.nq,
+            _check(self._apply2(mode | (self.nseg << MODE_SEG_SHIFT), self.affine_code, ptr(pb.latd), t.nq,
                                 ptr(t.wts),
                                 ptr(t.qpts), ptr(u), ptr(pold), ptr(pnew), ptr(x), ptr(y),
                                 ptr(self.yb), ptr(self.zb), ptr(self.cb), ptr(pb.xv),

@@ -1,5 +1,7 @@
 """ctypes signatures of libbdx_hip.so, one row per prototype of
-csrc/include/bdx_hip_api.h (tests/test_api_signatures.py compares the two)."""
+csrc/include/bdx_hip_api.h (tests/test_api_signatures.py compares the two),
+one `ctypes.Structure` per struct of the ABI and one table of its constants
+(tests/test_abi_layouts.py compares those with the headers)."""
 
 from __future__ import annotations
 
@@ -14,6 +16,100 @@ f32 = ctypes.c_float
 # degrees with a per-degree operator instance (BDX_FUSED_DEGREES / BDX_FUSED5_DEGREES)
 FUSED_DEGREES = range(1, 8)
 FUSED5_DEGREES = range(3, 8)
+
+# Constants of the headers under their C names (bdx_lattice.h, bdx_pmg_tail.h,
+# bdx_rt_setup.h, bdx_hip_api.h).
+CONSTANTS = {
+    "kLatticeWords": 21,
+    "kTailWords": 40, "kTailMaxLevels": 16, "kTailMaxNodes": 32768,
+    "kTailS": 21, "kTailDinv": 22, "kTailBc": 23, "kTailR": 24, "kTailZ": 25, "kTailD": 26,
+    "kTailY": 27, "kTailCidx": 28, "kTailCw": 29, "kTailFpos": 30, "kTailNcoef": 31,
+    "kTailCoef": 32,
+    "kBdxTransportNone": 0, "kBdxTransportRccl": 1, "kBdxTransportThread": 2,
+    "kBdxTransportEmulated": 3,
+    "kFusedModeSegShift": 8,
+}
+
+
+def _ptrs(*names):
+    return [(n, vp) for n in names]
+
+
+def _ints(*names):
+    return [(n, i32) for n in names]
+
+
+class Lattice(ctypes.Structure):
+    """BdxLattice: the packed int64 lattice descriptor, word for word."""
+    _fields_ = [("n", i64 * 3), ("L", i64 * 3), ("g0", i64 * 3), ("N", i64 * 3), ("gh", i64 * 3),
+                ("P", i64), ("ld", i64), ("tsy", i64), ("tsz", i64), ("tntz", i64), ("tcol", i64)]
+
+
+class TailLevelWords(ctypes.Structure):
+    """BdxTailLevelWords: one level of the V-cycle tail's table."""
+    _fields_ = [("lat", Lattice)] + [(n, i64) for n in (
+        "S", "dinv", "bc", "r", "z", "d", "y", "cidx", "cw", "fpos", "ncoef", "coef")] + [
+        ("pad", i64 * (CONSTANTS["kTailWords"] - CONSTANTS["kTailCoef"] - 1))]
+
+
+_Latd = i64 * CONSTANTS["kLatticeWords"]
+
+
+class BdxRtHalo(ctypes.Structure):
+    _fields_ = _ptrs("buf_a", "buf_b", "face_boxes", "ghost_boxes", "face_cnt", "ghost_cnt") + [
+        ("nface_boxes", i32), ("face_total", i64), ("nghost_boxes", i32), ("ghost_total", i64),
+        ("transport", i32), ("nranks", i32), ("rank", i32), ("group_id", i64)]
+
+
+class BdxRtFusedSetup(ctypes.Structure):
+    _fields_ = [("latd", _Latd), ("latd_tiled", _Latd), ("own", i64 * 3)] + _ints(
+        "is_f64", "version", "affine", "P", "nq", "nblocks", "nty", "ntz", "sy", "sz", "nseg",
+        "use_graph", "overlap") + [("kappa", f64)] + _ptrs(
+        "wts", "qpts", "tabs", "x", "r", "p_a", "p_b", "y", "yb", "zb", "cb", "xv", "kc", "scal",
+        "partials", "upart", "xt", "rt", "pat", "pbt", "yt") + [("halo", BdxRtHalo)]
+
+
+class BdxRtDofmapSetup(ctypes.Structure):
+    _fields_ = [("latd", _Latd)] + _ints(
+        "is_f64", "P", "nq", "geom", "n_inner", "n_outer", "use_graph", "overlap") + [
+        ("nvec", i64), ("kappa", f64)] + _ptrs(
+        "x", "r", "p_a", "p_b", "y", "scal", "partials", "upart", "tab", "inner", "outer", "cdofs",
+        "cverts", "coords", "flags", "G", "kc") + [("halo", BdxRtHalo)]
+
+
+class BdxRtPhases(ctypes.Structure):
+    _fields_ = [(n, f64) for n in (
+        "halo_fwd", "op_interior", "op_boundary", "halo_rev", "join_rev_add",
+        "reduce_allreduce_pap", "update_rr", "allreduce_rr", "iteration",
+        # offsets from the iteration start: the comm-stream chain (forward
+        # exchange, boundary tiles, reverse send) is hidden when it ends
+        # before the interior tiles on the compute stream do
+        "t_halo_fwd_done", "t_boundary_done", "t_halo_rev_done", "t_op_interior_done")]
+
+
+class BdxRtOverlapProbe(ctypes.Structure):
+    _fields_ = [(n, f64) for n in (
+        "chain_alone_ms", "interior_alone_ms", "chain_done_ms", "interior_done_ms",
+        "exchange_alone_ms", "fwd_exchange_done_ms")]
+
+
+class BdxRtPreflight(ctypes.Structure):
+    _fields_ = [("ms", f64), ("allreduce", f64)]
+
+
+class BdxRtCommPriority(ctypes.Structure):
+    _fields_ = _ints("least", "greatest", "comm_stream")
+
+
+# header struct name -> mirror
+STRUCTS = {"BdxLattice": Lattice, "BdxTailLevelWords": TailLevelWords,
+           **{c.__name__: c for c in (BdxRtHalo, BdxRtFusedSetup, BdxRtDofmapSetup, BdxRtPhases,
+                                      BdxRtOverlapProbe, BdxRtPreflight, BdxRtCommPriority)}}
+
+
+def fields(rec) -> dict:
+    """{field name: value} of a record of scalars, in the struct's order."""
+    return {n: getattr(rec, n) for n, _ in rec._fields_}
 
 
 def _d(lib, name, argtypes, restype=i32):
@@ -100,10 +196,8 @@ def declare(lib) -> None:
     # native CG runtime (runtime.hip)
     _d(lib, "bdx_rt_nccl_unique_id", [vp])
     _d(lib, "bdx_rt_rccl_selftest", [vp, i32, vp])
-    _d(lib, "bdx_rt_create", [i32, vp, vp, vp, f64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32,
-                              i64, vp, vp, vp], vp)
-    _d(lib, "bdx_rt_create_dofmap", [i32, vp, vp, i64, f64, vp, vp, vp, vp, i32, i32, i32, i64,
-                                     vp], vp)
+    _d(lib, "bdx_rt_create", [ctypes.POINTER(BdxRtFusedSetup), vp], vp)
+    _d(lib, "bdx_rt_create_dofmap", [ctypes.POINTER(BdxRtDofmapSetup), vp], vp)
     _d(lib, "bdx_dofmap_nblocks", [i32, i32])
     _d(lib, "bdx_dofmap_set_mfma", [i32])
     _d(lib, "bdx_dofmap_uses_mfma", [i32, i32])
@@ -111,13 +205,13 @@ def declare(lib) -> None:
     _d(lib, "bdx_rt_connect", [vp, vp, i32])
     _d(lib, "bdx_rt_comm_count", [vp])
     _d(lib, "bdx_rt_overlap", [vp])
-    _d(lib, "bdx_rt_comm_priority", [vp, vp])
-    _d(lib, "bdx_rt_preflight", [vp, f64, vp])
-    _d(lib, "bdx_rt_overlap_probe", [vp, i64, vp, i32, vp])
+    _d(lib, "bdx_rt_comm_priority", [vp, ctypes.POINTER(BdxRtCommPriority)])
+    _d(lib, "bdx_rt_preflight", [vp, f64, ctypes.POINTER(BdxRtPreflight)])
+    _d(lib, "bdx_rt_overlap_probe", [vp, i64, vp, i32, ctypes.POINTER(BdxRtOverlapProbe)])
     _d(lib, "bdx_rt_bind_x", [vp, vp])
     _d(lib, "bdx_rt_set_precond", [vp, vp, vp, vp, vp, vp, i32])
     _d(lib, "bdx_rt_wait", [vp])
-    _d(lib, "bdx_rt_profile", [vp, ctypes.c_long, vp, i32])
+    _d(lib, "bdx_rt_profile", [vp, ctypes.c_long, ctypes.POINTER(BdxRtPhases)])
     _d(lib, "bdx_rt_reset", [vp])
     _d(lib, "bdx_rt_iterate", [vp, ctypes.c_long])
     _d(lib, "bdx_rt_iterate_timed", [vp, ctypes.c_long, vp])

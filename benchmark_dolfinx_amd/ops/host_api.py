@@ -5,6 +5,8 @@ from __future__ import annotations
 
 import ctypes
 
+from .hip_api import BdxRtDofmapSetup, BdxRtFusedSetup
+
 vp = ctypes.c_void_p
 i32 = ctypes.c_int
 i64 = ctypes.c_int64
@@ -20,6 +22,8 @@ def _d(lib, name, argtypes, restype=None):
 
 def declare(lib) -> None:
     _d(lib, "bdx_host_version", [], i32)
+    _d(lib, "bdx_cpu_rt_fused_setup_ok", [ctypes.POINTER(BdxRtFusedSetup)], i32)
+    _d(lib, "bdx_cpu_rt_dofmap_setup_ok", [ctypes.POINTER(BdxRtDofmapSetup)], i32)
     _d(lib, "bdx_watchdog_selftest", [f64, f64, f64, vp, vp], i32)
     for suf, ft in (("f64", f64), ("f32", f32)):
         _d(lib, f"bdx_cpu_stiffness_{suf}",

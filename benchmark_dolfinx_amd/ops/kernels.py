@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import native
+from . import hip_api, native
 from .native import ptr
 
 
@@ -78,7 +78,8 @@ class HTransferTables:
     def check(self, latd_c, latd_f) -> None:
         """The tables' extents are those of the two lattice descriptors (the
         kernels index the tables by lattice node)."""
-        if tuple(latd_c[3:6]) != self.Lc or tuple(latd_f[3:6]) != self.Lf:
+        lc, lf = (hip_api.Lattice.from_buffer_copy(d) for d in (latd_c, latd_f))
+        if tuple(lc.L) != self.Lc or tuple(lf.L) != self.Lf:
             raise ValueError("h-transfer tables do not belong to this lattice pair")
 
 
@@ -116,8 +117,8 @@ class PmgTail:
     launch checks) and on the device (`dev`, read by the kernel).  Everything
     is uploaded here, once; the tensors the table points to are kept alive."""
 
-    WORDS = 40          # kTailWords
-    MAX_NODES = 32768   # kTailMaxNodes
+    WORDS = hip_api.CONSTANTS["kTailWords"]
+    MAX_NODES = hip_api.CONSTANTS["kTailMaxNodes"]
 
     def __init__(self, levels, dtype, device):
         from ..models.poisson import CSROperator  # models.poisson imports this module
@@ -126,27 +127,29 @@ class PmgTail:
         self.shape = tuple(levels[0].pb.lat.shape)
         W = self.WORDS
         tab = np.zeros(self.nlev * W + 2 * sum(len(lv.coef) for lv in levels), dtype=np.int64)
+        words = (hip_api.TailLevelWords * self.nlev).from_buffer(tab)  # the same bytes, by name
         coef = tab.view(np.float64)
         self.S, self._keep = [], []
         off = self.nlev * W
         for l, lv in enumerate(levels):
             S = torch.from_numpy(stencil27(CSROperator(lv.pb), lv.pb.lat)).to(device)
             self.S.append(S)
-            w = tab[l * W: (l + 1) * W]
-            w[:21] = lv.latd
-            vecs = [S, lv.dinv, lv.bc, lv.r, lv.z, lv.d, lv.y]
+            w = words[l]
+            w.lat = hip_api.Lattice.from_buffer_copy(lv.latd)
+            vecs = {"S": S, "dinv": lv.dinv, "bc": lv.bc, "r": lv.r, "z": lv.z, "d": lv.d, "y": lv.y}
             if l < self.nlev - 1:
                 lv.H.check(levels[l + 1].latd, lv.latd)
-                vecs += [lv.H.cidx, lv.H.cw, lv.H.fpos]
-            for v in vecs[:2] + vecs[3:7] + vecs[8:9]:
-                if v is not None and v.dtype != dtype:
+                vecs.update(cidx=lv.H.cidx, cw=lv.H.cw, fpos=lv.H.fpos)
+            for name, v in vecs.items():
+                if name not in ("bc", "cidx", "fpos") and v is not None and v.dtype != dtype:
                     raise TypeError(f"tail level {l}: expected {dtype} data, got {v.dtype}")
-            w[21: 21 + len(vecs)] = [ptr(v) for v in vecs]
-            w[31], w[32] = len(lv.coef), off
+                setattr(w, name, ptr(v))
+            w.ncoef, w.coef = len(lv.coef), off
             for a, b in lv.coef:
                 coef[off], coef[off + 1] = a, b
                 off += 2
-            self._keep.append(vecs)
+            self._keep.append(list(vecs.values()))
+        del w, words  # the table is plain words from here on
         self.nwords = int(tab.size)
         self.host = tab
         self.dev = torch.from_numpy(tab).to(device)

@@ -22,18 +22,16 @@ import os
 import numpy as np
 import torch
 
-from ..ops import native
+from ..ops import hip_api, native
 from ..ops.kernels import _check, _stream
 from ..ops.native import ptr
 
 
-PHASES = ("halo_fwd", "op_interior", "op_boundary", "halo_rev", "join_rev_add",
-          "reduce_allreduce_pap", "update_rr", "allreduce_rr", "iteration",
-          # offsets from the iteration start: the comm-stream chain (forward
-          # exchange, boundary tiles, reverse send) is hidden when it ends
-          # before the interior tiles on the compute stream do
-          "t_halo_fwd_done", "t_boundary_done", "t_halo_rev_done",
-          "t_op_interior_done")
+PHASES = tuple(n for n, _ in hip_api.BdxRtPhases._fields_)
+TRANSPORTS = {"none": hip_api.CONSTANTS["kBdxTransportNone"],
+              "rccl": hip_api.CONSTANTS["kBdxTransportRccl"],
+              "thread": hip_api.CONSTANTS["kBdxTransportThread"],
+              "emulated": hip_api.CONSTANTS["kBdxTransportEmulated"]}
 
 
 def _agree(comm, ok: bool) -> bool:
@@ -80,63 +78,85 @@ class NativeCGRuntime:
         self.kind = "dofmap" if getattr(op, "name", "") == "dofmap" else "fused"
         self.group = 0
         if comm.size == 1:
-            transport = 0
+            self.transport = "none"
         elif hasattr(comm, "g"):  # ThreadComm: ranks are threads of this process
-            transport = 2
+            self.transport = "thread"
             self.group = comm.g.uid  # unique per group: a reused id() could
             # pick up a stale group of a runtime that was not closed yet
         elif comm.backend == "nccl":
-            transport = 1
+            self.transport = "rccl"
         elif comm.backend == "emulated":  # EmulatedRankComm: modelled links
-            transport = 3
+            self.transport = "emulated"
             halo.buf_a.zero_()  # the emulated copies move finite data only
             halo.buf_b.zero_()
         else:
-            transport = -1
-        self.transport = {0: "none", 1: "rccl", 2: "thread", 3: "emulated"}.get(
-            transport, "unsupported")
+            self.transport = "unsupported"
         self.upart = torch.zeros(self.lib.bdx_hip_partials_size(), dtype=torch.float64,
                                  device=pb.device)
         self.x = cg.x
-        fo, gh = halo.owned_faces, halo.ghosts
-        self._hs = np.array([len(fo.boxes), fo.total, len(gh.boxes), gh.total], dtype=np.int64)
-        self._fc = np.array(fo.counts, dtype=np.int64)
-        self._gc = np.array(gh.counts, dtype=np.int64)
-        self._latd = np.ascontiguousarray(pb.latd, dtype=np.int64)
-        ok = transport >= 0 and comm.rank != self._inject_fail_rank
+        self._keep = []  # the tensors and arrays a setup record points to
+        ok = self.transport in TRANSPORTS and comm.rank != self._inject_fail_rank
         if self.kind == "dofmap":
-            ok = ok and self._create_dofmap(op, cg, use_graph, overlap, transport)
+            ok = ok and self._create_dofmap(op, cg, use_graph, overlap)
         else:
-            ok = ok and self._create_fused(op, cg, use_graph, overlap, transport)
-        self._connect(comm, ok, transport)
+            ok = ok and self._create_fused(op, cg, use_graph, overlap)
+        self._connect(comm, ok)
 
-    def _create_dofmap(self, op, cg, use_graph, overlap, transport) -> bool:
-        """The dofmap data model's loop (runtime.hip DofCGRuntime)."""
+    def _p(self, buf) -> int:
+        """The address of `buf` for a setup record; `buf` is kept alive."""
+        self._keep.append(buf)
+        return ptr(buf)
+
+    def _fill_common(self, s, cg, use_graph, overlap) -> None:
+        """What both setup records share: the descriptor, the flags, the CG
+        buffers and the halo record."""
         pb, halo = self.pb, self.pb.halo
+        s.latd[:] = [int(v) for v in pb.latd]
+        s.is_f64 = int(pb.dtype == torch.float64)
+        s.use_graph, s.overlap = int(use_graph), int(overlap)
+        s.kappa = float(pb.kappa)
+        s.x = self._p(cg.x)  # the first one kept: bind_x replaces it
+        s.r, s.y, s.scal = self._p(cg.r), self._p(cg.y), self._p(cg.scal)
+        s.upart = self._p(self.upart)
+        fo, gh, h = halo.owned_faces, halo.ghosts, s.halo
+        h.buf_a, h.buf_b = self._p(halo.buf_a), self._p(halo.buf_b)
+        h.face_boxes, h.ghost_boxes = self._p(fo.table), self._p(gh.table)
+        h.face_cnt = self._p(np.array(fo.counts, dtype=np.int64))
+        h.ghost_cnt = self._p(np.array(gh.counts, dtype=np.int64))
+        h.nface_boxes, h.face_total = len(fo.boxes), int(fo.total)
+        h.nghost_boxes, h.ghost_total = len(gh.boxes), int(gh.total)
+        h.transport = TRANSPORTS[self.transport]
+        h.nranks, h.rank, h.group_id = pb.comm.size, pb.comm.rank, self.group
+
+    def _create_dofmap(self, op, cg, use_graph, overlap) -> bool:
+        """The dofmap data model's loop (runtime.hip DofCGRuntime)."""
+        pb = self.pb
         self.tiled = False
-        self._ip = np.array([pb.degree, pb.tables.nq, op.geom, int(op.inner.numel()),
-                             int(op.outer.numel()), int(use_graph), int(overlap)], dtype=np.int32)
-        bufs = [cg.x, cg.r, op.p_a, op.p_b, cg.y, cg.scal, cg.partials, self.upart,
-                halo.buf_a, halo.buf_b, halo.owned_faces.table, halo.ghosts.table, op.tab,
-                op.inner, op.outer, op.cdofs, op.cverts, op.coords, op.flags, op.G, op.kc]
-        self._keep = bufs
-        self._ptrs = (ctypes.c_void_p * len(bufs))(*[ptr(b) for b in bufs])
-        self.h = self.lib.bdx_rt_create_dofmap(
-            int(pb.dtype == torch.float64), ptr(self._latd), ptr(self._ip), int(cg.r.numel()),
-            float(pb.kappa), self._ptrs, ptr(self._hs), ptr(self._fc), ptr(self._gc), transport,
-            pb.comm.size, pb.comm.rank, self.group, _stream())
+        s = hip_api.BdxRtDofmapSetup()
+        self._fill_common(s, cg, use_graph, overlap)
+        s.P, s.nq, s.geom = pb.degree, pb.tables.nq, op.geom
+        s.n_inner, s.n_outer = int(op.inner.numel()), int(op.outer.numel())
+        s.nvec = int(cg.r.numel())
+        s.p_a, s.p_b, s.partials = self._p(op.p_a), self._p(op.p_b), self._p(cg.partials)
+        s.tab = self._p(op.tab)
+        s.inner, s.outer = self._p(op.inner), self._p(op.outer)
+        s.cdofs, s.cverts = self._p(op.cdofs), self._p(op.cverts)
+        s.coords, s.flags = self._p(op.coords), self._p(op.flags)
+        s.G, s.kc = self._p(op.G), self._p(op.kc)
+        self.h = self.lib.bdx_rt_create_dofmap(ctypes.byref(s), _stream())
         return bool(self.h)
 
-    def _create_fused(self, op, cg, use_graph, overlap, transport) -> bool:
-        pb, halo = self.pb, self.pb.halo
+    def _create_fused(self, op, cg, use_graph, overlap) -> bool:
+        pb = self.pb
         t = op.t
-        self._own = np.array(pb.lat.owned_hi, dtype=np.int64)
-        self._ip = np.array([op.version, op.affine_code, pb.degree, t.nq, op.nblocks, op.nty,
-                             op.ntz, op.sy, op.sz, int(use_graph), int(overlap), op.nseg],
-                            dtype=np.int32)
-        self._wts = np.ascontiguousarray(t.wts, dtype=np.float64)
-        self._qpts = np.ascontiguousarray(t.qpts, dtype=np.float64)
-        fo, gh = halo.owned_faces, halo.ghosts
+        s = hip_api.BdxRtFusedSetup()
+        self._fill_common(s, cg, use_graph, overlap)
+        s.own[:] = [int(v) for v in pb.lat.owned_hi]
+        s.version, s.affine, s.P, s.nq = op.version, op.affine_code, pb.degree, t.nq
+        s.nblocks, s.nseg = op.nblocks, op.nseg
+        s.nty, s.ntz, s.sy, s.sz = op.nty, op.ntz, op.sy, op.sz
+        s.wts = self._p(np.ascontiguousarray(t.wts, dtype=np.float64))
+        s.qpts = self._p(np.ascontiguousarray(t.qpts, dtype=np.float64))
         # Tiled vector storage for the x-march kernels: each (y, z) tile's
         # patch of an x-plane is contiguous, so the kernels' writes are whole
         # lines (profiles/r2_march_bw.md).  BDX_TILED=0: the lattice layout;
@@ -151,26 +171,19 @@ class NativeCGRuntime:
         f3 = op.version == 3 and (mode == "2" or getattr(op, "x_trilinear", False))
         self.tiled = (mode != "0" and (op.version == 5 or f3)
                       and (op.sy * op.sz * esz) % 16 == 0)
-        self._latdT = None
-        self._tbufs = []
-        if self.tiled:
-            self._latdT = np.ascontiguousarray(pb.lat.as_int64((op.sy, op.sz)), dtype=np.int64)
+        if self.tiled:  # zeroed: the padding of the tiled vectors stays zero
+            s.latd_tiled[:] = [int(v) for v in pb.lat.as_int64((op.sy, op.sz))]
             n = pb.lat.tiled_size(op.sy, op.sz)
-            self._tbufs = [torch.zeros(n, dtype=pb.dtype, device=pb.device) for _ in range(5)]
-        self._tptrs = (ctypes.c_void_p * 5)(*[ptr(b) for b in self._tbufs]) if self.tiled else None
-        bufs = [cg.x, cg.r, op.p_old, op.p_new, cg.y, op.yb, op.zb, op.cb, pb.xv, cg.scal,
-                op.partials, self.upart, halo.buf_a, halo.buf_b, fo.table, gh.table, pb.kc]
-        self._keep = bufs + [op.tabs]
-        self._ptrs = (ctypes.c_void_p * len(bufs))(*[ptr(b) for b in bufs])
-        del fo, gh
-        self.h = self.lib.bdx_rt_create(
-            int(pb.dtype == torch.float64), ptr(self._latd), ptr(self._own), ptr(self._ip),
-            float(pb.kappa), ptr(self._wts), ptr(self._qpts), ptr(op.tabs), self._ptrs,
-            ptr(self._hs), ptr(self._fc), ptr(self._gc), transport, pb.comm.size, pb.comm.rank,
-            self.group, _stream(), ptr(self._latdT), self._tptrs)
+            s.xt, s.rt, s.pat, s.pbt, s.yt = (
+                self._p(torch.zeros(n, dtype=pb.dtype, device=pb.device)) for _ in range(5))
+        s.tabs = self._p(op.tabs)
+        s.p_a, s.p_b, s.partials = self._p(op.p_old), self._p(op.p_new), self._p(op.partials)
+        s.yb, s.zb, s.cb = self._p(op.yb), self._p(op.zb), self._p(op.cb)
+        s.xv, s.kc = self._p(pb.xv), self._p(pb.kc)
+        self.h = self.lib.bdx_rt_create(ctypes.byref(s), _stream())
         return bool(self.h)
 
-    def _connect(self, comm, ok: bool, transport: int) -> None:
+    def _connect(self, comm, ok: bool) -> None:
         """1) every rank created its runtime locally (no communication): agree;
         2) open the RCCL communicator (ncclUniqueId from rank 0 over the torch
         group), bounded by the watchdog deadline: agree again."""
@@ -181,7 +194,7 @@ class NativeCGRuntime:
                 f"for backend {comm.backend!r}, or an injected failure)")
         # 2) open the runtime's own RCCL communicator (ncclUniqueId from rank 0
         #    over the torch group); bounded by the watchdog deadline
-        if transport == 1:
+        if self.transport == "rccl":
             uid = (ctypes.c_char * 128)()
             good = True
             if comm.rank == 0:
@@ -202,21 +215,22 @@ class NativeCGRuntime:
     def comm_priority(self) -> dict:
         """Priority of the comm stream and the device's range (HIP: a lower
         value is a higher priority)."""
-        out = (ctypes.c_int * 3)()
-        _check(self.lib.bdx_rt_comm_priority(self.h, out), "rt_comm_priority")
-        return {"least": out[0], "greatest": out[1], "comm_stream": out[2]}
+        out = hip_api.BdxRtCommPriority()
+        _check(self.lib.bdx_rt_comm_priority(self.h, ctypes.byref(out)), "rt_comm_priority")
+        return hip_api.fields(out)
 
     def preflight(self, timeout_s: float = 60.0) -> dict:
         """One forward halo exchange and a device all-reduce of (rank + 1),
         bounded by `timeout_s`: raises if a peer never joins or the sum is
         wrong (every rank must call it)."""
-        out = (ctypes.c_double * 2)()
-        _check(self.lib.bdx_rt_preflight(self.h, float(timeout_s), out), "rt_preflight")
+        out = hip_api.BdxRtPreflight()
+        _check(self.lib.bdx_rt_preflight(self.h, float(timeout_s), ctypes.byref(out)),
+               "rt_preflight")
         n = self.pb.comm.size
         want = n * (n + 1) / 2
-        if out[1] != want:
-            raise RuntimeError(f"pre-flight all-reduce returned {out[1]}, expected {want}")
-        return {"ms": float(out[0]), "allreduce": float(out[1])}
+        if out.allreduce != want:
+            raise RuntimeError(f"pre-flight all-reduce returned {out.allreduce}, expected {want}")
+        return hip_api.fields(out)
 
     def overlap_probe(self, n: int, reps: int = 5) -> dict:
         """One-rank probe of the split schedule (runtime.hip overlap_probe):
@@ -225,16 +239,13 @@ class NativeCGRuntime:
         CG state (restart CG afterwards)."""
         buf = torch.zeros(2 * int(n), dtype=torch.float64, device=self.pb.device)
         buf[:n] = torch.arange(n, dtype=torch.float64, device=self.pb.device)
-        out = (ctypes.c_double * 6)()
+        out = hip_api.BdxRtOverlapProbe()
         torch.cuda.synchronize()
-        _check(self.lib.bdx_rt_overlap_probe(self.h, int(n), ptr(buf), int(reps), out),
-               "rt_overlap_probe")
+        _check(self.lib.bdx_rt_overlap_probe(self.h, int(n), ptr(buf), int(reps),
+                                             ctypes.byref(out)), "rt_overlap_probe")
         torch.cuda.synchronize()
-        ok = bool(torch.equal(buf[n:], buf[:n]))
-        keys = ("chain_alone_ms", "interior_alone_ms", "chain_done_ms", "interior_done_ms",
-                "exchange_alone_ms", "fwd_exchange_done_ms")
-        rec = {k: float(v) for k, v in zip(keys, out)}
-        rec["exchange_ok"] = ok
+        rec = hip_api.fields(out)
+        rec["exchange_ok"] = bool(torch.equal(buf[n:], buf[:n]))
         rec["bytes"] = int(n) * 8
         return rec
 
@@ -295,10 +306,10 @@ class NativeCGRuntime:
 
     def profile(self, n: int) -> dict:
         """n eager iterations with hipEvent phase timers -> mean ms per phase."""
-        out = (ctypes.c_double * len(PHASES))()
-        _check(self.lib.bdx_rt_profile(self.h, int(n), out, len(PHASES)), "rt_profile")
+        out = hip_api.BdxRtPhases()
+        _check(self.lib.bdx_rt_profile(self.h, int(n), ctypes.byref(out)), "rt_profile")
         self._sync_state()
-        ph = {k: float(v) for k, v in zip(PHASES, out)}
+        ph = hip_api.fields(out)
         # meaningful only for the split (two-stream) schedule
         split = self.overlap
         ph["halo_fwd_hidden"] = (ph["t_halo_fwd_done"] <= ph["t_op_interior_done"]) if split else None

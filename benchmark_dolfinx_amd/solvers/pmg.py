@@ -65,6 +65,7 @@ import torch
 from ..fem.mesh import _hash_uniform, h_hierarchy
 from ..fem.quadrature import lagrange_tables
 from ..models.poisson import PoissonProblem
+from ..ops.hip_api import CONSTANTS
 
 
 def level_degrees(P: int) -> list[int]:
@@ -134,7 +135,7 @@ class PMultigrid:
     level (None: no level qualifies, the cycle is the untailed one),
     `tail_levels` their number and `tail` the `ops.kernels.PmgTail`."""
 
-    TAIL_MAX_NODES = 32768
+    TAIL_MAX_NODES = CONSTANTS["kTailMaxNodes"]
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,

@@ -41,6 +41,9 @@ def _kind(ctype: str):
     """ctypes kind of a C type (without a parameter name)."""
     t = " ".join(ctype.replace("*", " * ").split())
     if "*" in t:
+        base = t.replace("const", "").replace("*", "").strip()
+        if base in hip_api.STRUCTS:  # a record of the ABI: a pointer to its mirror, not void*
+            return ctypes.POINTER(hip_api.STRUCTS[base])
         return ctypes.c_char_p if t in ("char *", "const char *") else ctypes.c_void_p
     words = [w for w in t.split() if w != "const"]
     assert len(words) == 1 and words[0] in _VALUE_KINDS, f"unmapped C type {ctype!r}"
@@ -102,7 +105,7 @@ def tables(request):
 def test_headers_declare_the_known_entry_points(tables):
     lib, protos, _ = tables
     assert len(protos) > (100 if lib == "hip" else 30)
-    probe = {"hip": ("bdx_rt_create", ctypes.c_void_p, 19), "host": ("bdx_cpu_csr_f32", ctypes.c_int64, 13)}
+    probe = {"hip": ("bdx_rt_create", ctypes.c_void_p, 2), "host": ("bdx_cpu_csr_f32", ctypes.c_int64, 13)}
     name, ret, nargs = probe[lib]
     assert protos[name][0] is ret and len(protos[name][1]) == nargs
 
