@@ -73,7 +73,7 @@ def _fill(pb, glob, fill=NAN):
     node (ghost planes included) and `fill` in the storage padding."""
     v = np.full(pb.lat.shape, fill, dtype=np.float64)
     v[:, :, : pb.lat.L[2]] = glob.ravel()[pb.lat.global_indices()]
-    return torch.from_numpy(v).to(pb.dtype)
+    return torch.from_numpy(v).to(pb.dtype).to(pb.device)
 
 
 def _glob(pb, v):
@@ -84,8 +84,8 @@ def _bits(t):
     return t.contiguous().view(torch.int64 if t.element_size() == 8 else torch.int32)
 
 
-def _problem(nc, P, dt=torch.float64, pert=0.0, coef="constant", comm=None):
-    return PoissonProblem(comm or Comm(), nc, P, 1, False, dt, "cpu", pert, coef)
+def _problem(nc, P, dt=torch.float64, pert=0.0, coef="constant", comm=None, platform="cpu"):
+    return PoissonProblem(comm or Comm(), nc, P, 1, False, dt, platform, pert, coef)
 
 
 @functools.lru_cache(maxsize=None)
@@ -169,8 +169,8 @@ def test_raw_restrict_keeps_dirichlet_sums_and_rejects_bad_pairs():
 
 
 # ------------------------------------------------------- 2. adjointness
-def _adjoint_gap(comm, nc, Pf, dt):
-    pmg = PMultigrid(_problem(nc, Pf, dt, comm=comm))
+def _adjoint_gap(comm, nc, Pf, dt, platform="cpu"):
+    pmg = PMultigrid(_problem(nc, Pf, dt, comm=comm, platform=platform))
     Pc = pmg.degrees[1]
     fine, coarse = pmg.levels[0].pb, pmg.levels[1].pb
     gu, gv = _random(_shape(nc, Pc), 11, dt), _random(_shape(nc, Pf), 13, dt)
@@ -181,9 +181,11 @@ def _adjoint_gap(comm, nc, Pf, dt):
     pu, rv = fine.new_vector(), coarse.new_vector()
     pmg.restrict(0, vf, rv)
     # R zeroes Dirichlet rows: compare on a u that vanishes there
-    uc[:, :, : coarse.lat.L[2]][torch.from_numpy(coarse.lat.bc_mask())] = 0.0
+    uc[:, :, : coarse.lat.L[2]][torch.from_numpy(coarse.lat.bc_mask()).to(uc.device)] = 0.0
     pmg.prolong(0, uc, pu)
-    return fine.inner(pu, vf), coarse.inner(uc, rv), Pc, gu, gv
+    gap = fine.inner(pu, vf), coarse.inner(uc, rv), Pc, gu, gv
+    pmg.close()
+    return gap
 
 
 def _adjoint_bound(nc, Pf, Pc, gu, gv, dt):
@@ -242,8 +244,8 @@ def test_prolong_reproduces_polynomials(Pf, Pc, dt):
 
 
 # --------------------------------- 4. restriction is partition-invariant
-def _rank_restrict(comm, nc, Pf):
-    pmg = PMultigrid(_problem(nc, Pf, comm=comm))
+def _rank_restrict(comm, nc, Pf, platform="cpu"):
+    pmg = PMultigrid(_problem(nc, Pf, comm=comm, platform=platform))
     fine, coarse = pmg.levels[0].pb, pmg.levels[1].pb
     vf = _fill(fine, _random(_shape(nc, Pf), 17, torch.float64))
     o = fine.lat.owned_hi
@@ -252,7 +254,9 @@ def _rank_restrict(comm, nc, Pf):
     pmg.restrict(0, vf, vc)
     # forwarded: the coarse ghost planes hold their owners' values
     gi = coarse.lat.global_indices()
-    return _glob(coarse, vc), (gi, vc[:, :, : coarse.lat.L[2]].numpy().copy())
+    out = _glob(coarse, vc), (gi, vc[:, :, : coarse.lat.L[2]].cpu().numpy().copy())
+    pmg.close()
+    return out
 
 
 @pytest.mark.parametrize("Pf,Pc", [(3, 1), (4, 2), (6, 3)])
