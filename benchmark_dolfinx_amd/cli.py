@@ -18,7 +18,9 @@ its smoothers / of its coarsest-level solve; --pmg_hlevels N: geometric
 h-levels under its degree-1 level, -1 = as many as the mesh allows;
 --pmg_float {32,64}: precision of its V-cycle, 32 under --float 64 = the
 mixed-precision solve; --pmg_tail N: its trailing degree-1 levels of at most
-N nodes run in one kernel launch, one rank only),
+N nodes run in one kernel launch, one rank only; --pmg_transfer {cell,row}:
+the transfer kernels between its p-levels, row = the row-streaming ones that
+fold the residual and the update),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -96,6 +98,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Run the trailing degree-1 levels of the p-multigrid V-cycle that have "
                          "at most N local nodes in one kernel launch (--cg --precond pmg, one "
                          "rank): 0 = off, N <= 32768")
+    ap.add_argument("--pmg_transfer", default="cell", choices=["cell", "row"],
+                    help="Transfer kernels between the p-multigrid's p-levels (--cg --precond "
+                         "pmg): cell = per cell; row = by lattice rows, one restriction that "
+                         "folds the residual and one prolongation that folds the update")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -120,6 +126,8 @@ def parse_args(argv=None):
         raise SystemExit("error: Option 'pmg_tail' must be 0 or a node count up to 32768")
     if args.pmg_tail != 0 and not (args.cg and args.precond == "pmg"):
         raise SystemExit("error: Option 'pmg_tail' needs 'cg' and 'precond pmg'")
+    if args.pmg_transfer != "cell" and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_transfer' needs 'cg' and 'precond pmg'")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
@@ -232,6 +240,8 @@ def run_benchmark(comm, nx, args, platform):
         pmg_opts["cycle_dtype"] = torch.float64 if args.pmg_float == 64 else torch.float32
     if args.pmg_tail != 0:
         pmg_opts["tail_nodes"] = args.pmg_tail
+    if args.pmg_transfer != "cell":
+        pmg_opts["p_transfer"] = args.pmg_transfer
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,

@@ -6,7 +6,8 @@
 // with.  The h-transfers, the Chebyshev step, the 27-point stencil and the
 // V-cycle tail are loops over the per-node bodies of
 // csrc/include/bdx_mg_bodies.h, which the device kernels map to threads; the
-// p-transfers keep a per-cell sum-factorised structure of their own.
+// p-transfers keep a per-cell sum-factorised structure of their own, and the
+// p-transfers by rows loop over the index helpers of the same header.
 
 #include <cstdint>
 
@@ -120,6 +121,101 @@ int restrict_host(const int64_t* latc, const int64_t* latf, const double* Jd, co
           }
     }
   }
+  return 0;
+}
+
+// ------------------------------------------- p-multigrid transfers by rows
+// Host twins of csrc/hip/lap_rowtransfer.h with its index helpers
+// (bdx_mg_bodies.h) and its summation order: the x-y combination of the rows
+// first (I outermost, then J, ascending, zero weights skipped), then z
+// ascending.
+
+// A pair transfer_pair_ok accepts, no null pointer; the table in T.
+template <typename T>
+bool rowtransfer_setup(const int64_t* latc, const int64_t* latf, const double* Jd, const void* src,
+                       const void* dst, BdxLattice& lc, BdxLattice& lf, T (&J)[8 * 4]) {
+  if (!latc || !latf || !Jd || !src || !dst) return false;
+  lc = BdxLattice::from(latc);
+  lf = BdxLattice::from(latf);
+  if (!transfer_pair_ok(lc, lf)) return false;
+  for (int i = 0; i < (lf.P + 1) * (lc.P + 1); ++i) J[i] = static_cast<T>(Jd[i]);
+  return true;
+}
+
+// add = 0: vf = P vc on every local fine node; add: vf += P vc on the owned ones.
+template <typename T>
+int prolong_row_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vc,
+                     T* vf, int add) {
+  BdxLattice lc, lf;
+  T J[8 * 4];
+  if (!rowtransfer_setup<T>(latc, latf, Jd, vc, vf, lc, lf, J)) return 1;
+  if (lf.n[0] == 0 || lf.n[1] == 0 || lf.n[2] == 0) return 0;
+  const int64_t PF = lf.P, PC = lc.P, NC = PC + 1;
+  const int64_t e[3] = {add ? lf.L[0] - lf.gh[0] : lf.L[0], add ? lf.L[1] - lf.gh[1] : lf.L[1],
+                        add ? lf.L[2] - lf.gh[2] : lf.L[2]};
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t I = 0; I < e[0]; ++I)
+    for (int64_t Jr = 0; Jr < e[1]; ++Jr) {
+      int64_t cx, qx, cy, qy;
+      ptransfer_cell(I, PF, lf.n[0], cx, qx);
+      ptransfer_cell(Jr, PF, lf.n[1], cy, qy);
+      for (int64_t k = 0; k < e[2]; ++k) {
+        int64_t cz, qz;
+        ptransfer_cell(k, PF, lf.n[2], cz, qz);
+        T out = 0;
+        for (int64_t c = 0; c < NC; ++c) {
+          T t = 0;
+          for (int64_t a = 0; a < NC; ++a)
+            for (int64_t b = 0; b < NC; ++b) {
+              const T w = J[qx * NC + a] * J[qy * NC + b];
+              if (w == 0) continue;
+              t += w * vc[lc.idx(cx * PC + a, cy * PC + b, cz * PC + c)];
+            }
+          out += J[qz * NC + c] * t;
+        }
+        const int64_t to = lf.idx(I, Jr, k);
+        vf[to] = add ? vf[to] + out : out;
+      }
+    }
+  return 0;
+}
+
+// vc = P^T (vf - y) (y null: P^T vf) on every local coarse node, from the
+// owned fine nodes.
+template <typename T>
+int restrict_row_host(const int64_t* latc, const int64_t* latf, const double* Jd, const T* vf,
+                      const T* y, T* vc) {
+  BdxLattice lc, lf;
+  T J[8 * 4];
+  if (!rowtransfer_setup<T>(latc, latf, Jd, vf, vc, lc, lf, J)) return 1;
+  if (lf.n[0] == 0 || lf.n[1] == 0 || lf.n[2] == 0) return 0;
+  const int64_t PF = lf.P, PC = lc.P;
+  const int64_t own[3] = {lf.L[0] - lf.gh[0], lf.L[1] - lf.gh[1], lf.L[2] - lf.gh[2]};
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int64_t A = 0; A < lc.L[0]; ++A)
+    for (int64_t B = 0; B < lc.L[1]; ++B) {
+      int64_t ilo, ihi, jlo, jhi;
+      ptransfer_support(A, PF, PC, lf.n[0], own[0], ilo, ihi);
+      ptransfer_support(B, PF, PC, lf.n[1], own[1], jlo, jhi);
+      for (int64_t C = 0; C < lc.L[2]; ++C) {
+        int64_t klo, khi;
+        ptransfer_support(C, PF, PC, lf.n[2], own[2], klo, khi);
+        T out = 0;
+        for (int64_t k = klo; k <= khi; ++k) {
+          T s = 0;
+          for (int64_t I = ilo; I <= ihi; ++I)
+            for (int64_t Jr = jlo; Jr <= jhi; ++Jr) {
+              const T w = ptransfer_weight<T>(J, I, A, PF, PC, lf.n[0]) *
+                          ptransfer_weight<T>(J, Jr, B, PF, PC, lf.n[1]);
+              if (w == 0) continue;
+              const int64_t at = lf.idx(I, Jr, k);
+              s += w * (y ? vf[at] - y[at] : vf[at]);
+            }
+          out += ptransfer_weight<T>(J, k, C, PF, PC, lf.n[2]) * s;
+        }
+        vc[lc.idx(A, B, C)] = out;
+      }
+    }
   return 0;
 }
 
@@ -273,6 +369,12 @@ extern "C" {
   }                                                                           \
   int bdx_cpu_hrestrict_##SUF BDX_P_CPU_HRESTRICT(T) {                        \
     return hrestrict_host<T>(latc, latf, cidx, cw, fpos, vf, y, vc);          \
+  }                                                                           \
+  int bdx_cpu_prolong_row_##SUF BDX_P_CPU_PROLONG_ROW(T) {                    \
+    return prolong_row_host<T>(latc, latf, J, vc, vf, add);                   \
+  }                                                                           \
+  int bdx_cpu_restrict_row_##SUF BDX_P_CPU_RESTRICT_ROW(T) {                  \
+    return restrict_row_host<T>(latc, latf, J, vf, y, vc);                    \
   }                                                                           \
   void bdx_cpu_cheb_step_##SUF BDX_P_CPU_CHEB_STEP(T) {                       \
     cheb_step_host<T>(L1, ld, o0, o1, o2, first, static_cast<T>(a),           \

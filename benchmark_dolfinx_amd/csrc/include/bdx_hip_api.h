@@ -304,6 +304,21 @@ BDX_TWINS(int, bdx_hprolong, BDX_P_HPROLONG)
   const T* vf, const T* y, T* vc, hipStream_t st)
 BDX_TWINS(int, bdx_hrestrict, BDX_P_HRESTRICT)
 
+// ------------------------------------------------- lap_rowtransfer_<suf>.hip
+// p-multigrid transfers by lattice rows, with the h-transfers' modes: vf = P vc
+// on every local fine node (add = 0) or vf += P vc on the owned ones (add = 1),
+// and vc = P^T (vf - y) (y may be null: P^T vf) over the owned fine nodes,
+// every local coarse node written by one launch.  latc, latf, J: as for
+// bdx_prolong.  hipErrorInvalidValue for a pair bdx_prolong refuses or a null
+// pointer, before anything is launched.
+#define BDX_P_PROLONG_ROW(T) (const int64_t* latc, const int64_t* latf, const double* J, const T* vc, T* vf, \
+  int add, hipStream_t st)
+BDX_TWINS(int, bdx_prolong_row, BDX_P_PROLONG_ROW)
+// (see bdx_prolong_row)
+#define BDX_P_RESTRICT_ROW(T) (const int64_t* latc, const int64_t* latf, const double* J, const T* vf, const T* y, \
+  T* vc, hipStream_t st)
+BDX_TWINS(int, bdx_restrict_row, BDX_P_RESTRICT_ROW)
+
 // --------------------------------------------------------- pmg_tail_<suf>.hip
 // z = the V-cycle from the first level of the table down and back up, applied
 // to r (the table's other vectors are work space); htab / dtab: the host and

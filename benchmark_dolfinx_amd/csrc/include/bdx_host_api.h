@@ -91,6 +91,16 @@ BDX_HOST_TWINS(int, bdx_cpu_hprolong, BDX_P_CPU_HPROLONG)
 #define BDX_P_CPU_HRESTRICT(T) (const int64_t* latc, const int64_t* latf, const int* cidx, const T* cw, \
   const int* fpos, const T* vf, const T* y, T* vc)
 BDX_HOST_TWINS(int, bdx_cpu_hrestrict, BDX_P_CPU_HRESTRICT)
+// p-multigrid transfers by lattice rows: vf (+)= P vc, vc = P^T (vf - y) (y may
+// be null); the host twins of bdx_prolong_row / bdx_restrict_row, nonzero for
+// a bad pair or a null pointer.
+#define BDX_P_CPU_PROLONG_ROW(T) (const int64_t* latc, const int64_t* latf, const double* J, const T* vc, T* vf, \
+  int add)
+BDX_HOST_TWINS(int, bdx_cpu_prolong_row, BDX_P_CPU_PROLONG_ROW)
+// (see bdx_cpu_prolong_row)
+#define BDX_P_CPU_RESTRICT_ROW(T) (const int64_t* latc, const int64_t* latf, const double* J, const T* vf, \
+  const T* y, T* vc)
+BDX_HOST_TWINS(int, bdx_cpu_restrict_row, BDX_P_CPU_RESTRICT_ROW)
 // Chebyshev step d = a d + b dinv (r - y); z += d (first: d = z = b dinv r),
 // the host twin of bdx_cheb_step.
 #define BDX_P_CPU_CHEB_STEP(T) (int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2, int first, double a, \

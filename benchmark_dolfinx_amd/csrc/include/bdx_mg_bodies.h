@@ -8,6 +8,8 @@
 //
 //   h-transfers   trilinear interpolation in index space between two degree-1
 //                 lattices and its transpose (tables: lap_htransfer.h)
+//   p-transfers by rows   the index helpers of lap_rowtransfer.h: cell and
+//                 local index of a fine node, support and weights of a coarse one
 //   stencil27     one row of a level's assembled 27-point operator
 //   cheb_entry    one entry of a Chebyshev-Jacobi step
 // and the checks of a level pair of the p- and the h-transfers.
@@ -28,6 +30,47 @@ BDX_HD bool transfer_pair_ok(const BdxLattice& lc, const BdxLattice& lf) {
     if (lc.L[a] != lc.n[a] * lc.P + 1 || lf.L[a] != lf.n[a] * lf.P + 1) return false;
   }
   return lc.ld >= lc.L[2] && lf.ld >= lf.L[2];
+}
+
+// p-transfers by rows (csrc/hip/lap_rowtransfer.h), one axis of n cells with
+// the degrees Pf / Pc and J the (Pf + 1) x (Pc + 1) table.  Fine node I
+// belongs to cell min(I / Pf, n - 1) with local index q = I - cell Pf, and its
+// weights are row q of J.  The first and the last row of J are unit vectors,
+// so a fine vertex node weighs 1 in its coarse vertex and 0 everywhere else:
+// every fine dof is counted once without a `take` rule.
+BDX_HD void ptransfer_cell(int64_t I, int64_t Pf, int64_t n, int64_t& cell, int64_t& q) {
+  cell = I / Pf;
+  if (cell > n - 1) cell = n - 1;
+  q = I - cell * Pf;
+}
+
+// Range [lo, hi] of the fine nodes coarse node A gathers, clipped to the owned
+// fine nodes (index < own): a cell-interior coarse node takes the Pf - 1
+// interior nodes of its cell, a coarse vertex those of each adjacent cell and
+// itself.
+BDX_HD void ptransfer_support(int64_t A, int64_t Pf, int64_t Pc, int64_t n, int64_t own,
+                              int64_t& lo, int64_t& hi) {
+  int64_t c = A / Pc;
+  if (c > n - 1) c = n - 1;
+  const int64_t a = A - c * Pc;
+  lo = c * Pf + 1;
+  hi = c * Pf + Pf - 1;
+  if (a == 0) lo = c > 0 ? lo - Pf : 0;
+  if (a == Pc) {
+    lo = c * Pf + 1;
+    hi = c * Pf + Pf;
+  }
+  if (hi > own - 1) hi = own - 1;
+}
+
+// Weight of fine node I in coarse node A: J[q][A - cell Pc], 0 where A is no
+// node of I's cell.
+template <typename T>
+BDX_HD T ptransfer_weight(const T* J, int64_t I, int64_t A, int64_t Pf, int64_t Pc, int64_t n) {
+  int64_t cell, q;
+  ptransfer_cell(I, Pf, n, cell, q);
+  const int64_t a = A - cell * Pc;
+  return a >= 0 && a <= Pc ? J[q * (Pc + 1) + a] : T(0);
 }
 
 // h-transfers: two degree-1 descriptors in the lattice layout on the same

@@ -43,6 +43,8 @@ def declare(lib) -> None:
         _d(lib, f"bdx_cpu_restrict_{suf}", [vp, vp, vp, vp, vp], i32)
         _d(lib, f"bdx_cpu_hprolong_{suf}", [vp, vp, vp, vp, vp, vp, vp, i32], i32)
         _d(lib, f"bdx_cpu_hrestrict_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp], i32)
+        _d(lib, f"bdx_cpu_prolong_row_{suf}", [vp, vp, vp, vp, vp, i32], i32)
+        _d(lib, f"bdx_cpu_restrict_row_{suf}", [vp, vp, vp, vp, vp, vp], i32)
         _d(lib, f"bdx_cpu_cheb_step_{suf}",
            [i64, i64, i64, i64, i64, i32, f64, f64, vp, vp, vp, vp, vp])
         _d(lib, f"bdx_cpu_pmg_tail_{suf}", [vp, i32, i64, vp, vp], i32)

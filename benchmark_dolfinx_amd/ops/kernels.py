@@ -321,6 +321,18 @@ class HipKernels:
         _check(self._f("bdx_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc),
                                        _stream()), "restrict")
 
+    def prolong_row(self, latd_c, J, vc, vf, add: bool = False):
+        """`prolong` by lattice rows (lap_rowtransfer.h): vf = P vc on every
+        local fine node, or with `add` vf += P vc on the owned ones."""
+        _check(self._f("bdx_prolong_row")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vc), ptr(vf),
+                                          int(add), _stream()), "prolong_row")
+
+    def restrict_row(self, latd_c, J, vf, y, vc):
+        """vc = P^T (vf - y) over the owned fine nodes (y None: P^T vf), every
+        local coarse node written; one launch, no zeroing, no atomics."""
+        _check(self._f("bdx_restrict_row")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(y),
+                                           ptr(vc), _stream()), "restrict_row")
+
     def hprolong(self, latd_c, tab: HTransferTables, vc, vf, add: bool = False):
         """h-multigrid: vf = P vc on every node of this (fine, degree-1)
         lattice, or with `add` vf += P vc on its owned nodes (lap_htransfer.h)."""
@@ -419,6 +431,16 @@ class HostKernels:
     def restrict(self, latd_c, J, vf, vc):
         if self._f("bdx_cpu_restrict")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(vc)):
             raise ValueError("restrict: lattice pair outside the p-multigrid schedule")
+
+    def prolong_row(self, latd_c, J, vc, vf, add: bool = False):
+        if self._f("bdx_cpu_prolong_row")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vc), ptr(vf),
+                                          int(add)):
+            raise ValueError("prolong_row: lattice pair outside the p-multigrid schedule")
+
+    def restrict_row(self, latd_c, J, vf, y, vc):
+        if self._f("bdx_cpu_restrict_row")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vf), ptr(y),
+                                           ptr(vc)):
+            raise ValueError("restrict_row: lattice pair outside the p-multigrid schedule")
 
     def hprolong(self, latd_c, tab: HTransferTables, vc, vf, add: bool = False):
         tab.check(latd_c, self.latd)

@@ -55,6 +55,13 @@ stencil (`ops.kernels.stencil27` of `CSROperator`), which equals the
 matrix-free operator to rounding, not bitwise: the tailed preconditioner is a
 rounding-level perturbation of the untailed one.  One rank only: the tail
 levels of a partitioned mesh would need halo exchanges inside the kernel.
+
+Row transfers (`p_transfer="row"`, off by default): the p-pairs use the
+row-streaming kernels of csrc/hip/lap_rowtransfer.h, which have the
+h-transfers' modes, so a p-pair runs the h-pair's branch of the cycle: one
+restriction that folds the residual and one prolongation that folds the
+update, with no axpy, no zeroing and no colour launches.  The operators are
+those of the cell kernels in another summation order.
 """
 
 from __future__ import annotations
@@ -133,13 +140,18 @@ class PMultigrid:
     tail_nodes: 0 = off; N > 0 = the levels of the tail (module docstring) run
     in one `pmg_tail` call; `tail_start` is then the index of the tail's first
     level (None: no level qualifies, the cycle is the untailed one),
-    `tail_levels` their number and `tail` the `ops.kernels.PmgTail`."""
+    `tail_levels` their number and `tail` the `ops.kernels.PmgTail`.
+
+    p_transfer: "cell" = the per-cell transfer kernels between the p-levels;
+    "row" = the row-streaming ones (module docstring), which accept `add` and
+    `y` in `prolong` / `restrict` as the h-pairs do."""
 
     TAIL_MAX_NODES = CONSTANTS["kTailMaxNodes"]
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
-                 h_levels: int = 0, cycle_dtype: torch.dtype | None = None, tail_nodes: int = 0):
+                 h_levels: int = 0, cycle_dtype: torch.dtype | None = None, tail_nodes: int = 0,
+                 p_transfer: str = "cell"):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
@@ -153,6 +165,9 @@ class PMultigrid:
         if tail_nodes > 0 and pb.comm.size > 1:
             raise ValueError("tail_nodes needs a single rank: the tail levels of a partitioned "
                              "mesh would need halo exchanges inside the kernel")
+        if p_transfer not in ("cell", "row"):
+            raise ValueError(f"p_transfer must be 'cell' or 'row', got {p_transfer!r}")
+        self.p_transfer = p_transfer
         if cycle_dtype is None:
             cycle_dtype = pb.dtype
         if cycle_dtype not in (torch.float32, torch.float64) or \
@@ -248,11 +263,15 @@ class PMultigrid:
     def prolong(self, l: int, vc: torch.Tensor, vf: torch.Tensor, add: bool = False) -> None:
         """vf = P vc from level l + 1 to level l (every local fine node; the
         coarse ghost planes are read, so vc is forward-exchanged first).
-        `add` (h-pairs only): vf += P vc on the owned fine nodes instead."""
+        `add` (h-pairs, and p-pairs with p_transfer="row"): vf += P vc on the
+        owned fine nodes instead."""
         fine, coarse = self.levels[l], self.levels[l + 1]
         coarse.pb.halo.forward(vc)
         if fine.H is not None:
             fine.k.hprolong(coarse.latd, fine.H, vc, vf, add)
+            return
+        if self.p_transfer == "row":
+            fine.k.prolong_row(coarse.latd, fine.J, vc, vf, add)
             return
         if add:
             raise ValueError("prolong(add=True) is the h-transfer's mode")
@@ -263,10 +282,12 @@ class PMultigrid:
         """vc = P^T vf from level l to level l + 1: owned fine dofs only, the
         partial sums on the coarse ghost planes reverse-exchanged to their
         owners, Dirichlet entries zeroed, then forwarded to the ghosts.
-        `y` (h-pairs only): vc = P^T (vf - y)."""
+        `y` (h-pairs, and p-pairs with p_transfer="row"): vc = P^T (vf - y)."""
         fine, coarse = self.levels[l], self.levels[l + 1]
         if fine.H is not None:
             fine.k.hrestrict(coarse.latd, fine.H, vf, y, vc)
+        elif self.p_transfer == "row":
+            fine.k.restrict_row(coarse.latd, fine.J, vf, y, vc)
         else:
             if y is not None:
                 raise ValueError("restrict(y=) is the h-transfer's mode")
@@ -296,9 +317,9 @@ class PMultigrid:
             return
         nxt = self.levels[l + 1]
         lv.op.apply(z, lv.y)
-        if lv.H is not None:
-            # h-pair: the residual and the correction's sum are folded into
-            # the transfer kernels' load and store
+        if lv.H is not None or self.p_transfer == "row":
+            # h-pair, or a p-pair by rows: the residual and the correction's
+            # sum are folded into the transfer kernels' load and store
             self.restrict(l, r, nxt.r, lv.y)    # r_c = R (r - A z)
             self._vcycle(l + 1, nxt.r, nxt.z)
             self.prolong(l, nxt.z, z, True)     # z += P z_c
@@ -337,6 +358,8 @@ class PMultigrid:
         if self.tail_nodes != 0:
             out["tail_nodes"] = self.tail_nodes
             out["tail_levels"] = self.tail_levels
+        if self.p_transfer != "cell":
+            out["p_transfer"] = self.p_transfer
         return out
 
     def close(self) -> None:

@@ -9,6 +9,10 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
                                                              (FP32 cycles, profiles/pmg_mixed.md)
   python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --tail 512,4096,32768 --no-yardsticks
                                                              (one-launch tail, profiles/pmg_tail.md)
+  python scripts/pmg_compare.py --hlevels -1 --transfer cell,row --cycle_float 32 --no-yardsticks
+                                                             (row transfers, profiles/pmg_rowtransfer.md)
+  python scripts/pmg_compare.py --degree 6 --transfer-kernels
+                                                             (their kernels against the launches they replace)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -27,6 +31,19 @@ its own auto-selected operator:
   hpmg32_tN  trailing small levels in one launch (csrc/hip/pmg_tail.h), and the same for hpmg32;
              interleaved like hpmg.  The "tail" block also times the tail's one call against
              the untailed `_vcycle` of the same levels, with device events
+
+  <v>_row    (--transfer cell,row) every pmg variant v again with PMultigrid(p_transfer="row"):
+             the row-streaming transfers between the p-levels (csrc/hip/lap_rowtransfer.h);
+             interleaved like hpmg, so the yardstick of v_row is v in the same process
+
+--transfer-kernels: no solve.  For every p-pair of the configured problem, in FP64 and FP32
+vectors, device-event times (the median of --reps batches of five calls, the candidates
+interleaved batch by batch) of
+  restrict   axpy (t = r - y) + zero_ + restrict (eight colour launches)   against
+             restrict_row with y;   compulsory bytes: two fine reads + one coarse write
+  prolong    prolong + axpy (z += t)   against   prolong_row with add;
+             compulsory bytes: one coarse read + one fine read + one fine write
+with the effective TB/s over the compulsory bytes and the 2-read 1-write stream rate.
 
 Per-iteration time: device events between the steps of `iterate_timed(n)`, per
 window the mean of the first n - 1 steps, per variant the median over the
@@ -55,6 +72,86 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def transfer_kernels(a, nx) -> dict:
+    """--transfer-kernels (module docstring): one record with a block per
+    vector type and p-pair."""
+    import numpy as np
+    import torch
+
+    from benchmark_dolfinx_amd.fem.quadrature import lagrange_tables
+    from benchmark_dolfinx_amd.models.poisson import PoissonProblem
+    from benchmark_dolfinx_amd.parallel.comm import Comm
+    from benchmark_dolfinx_amd.solvers.pmg import level_degrees
+
+    def batch(fn):
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        for _ in range(5):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / 5
+
+    def interleaved(fns):
+        """Median ms per call of each candidate, one batch of each in turn."""
+        for fn in fns.values():
+            fn()
+        torch.cuda.synchronize()
+        out = {k: [] for k in fns}
+        for _ in range(a.reps):
+            for k, fn in fns.items():
+                out[k].append(batch(fn))
+        return {k: {"median": statistics.median(v), "min": min(v), "max": max(v)}
+                for k, v in out.items()}
+
+    rec = {"degree": a.degree, "perturb": a.perturb, "kappa": a.kappa, "mesh": list(nx),
+           "device": torch.cuda.get_device_name(0), "pairs": []}
+    degrees = level_degrees(a.degree)
+    for dt, size in ((torch.float64, 8), (torch.float32, 4)):
+        pbs = [PoissonProblem(Comm(), nx, P, 1, False, dt, "gpu", a.perturb, a.kappa)
+               for P in degrees]
+        for fine, coarse in zip(pbs, pbs[1:]):
+            J = np.ascontiguousarray(
+                lagrange_tables(coarse.tables.nodes, fine.tables.nodes)[0], dtype=np.float64)
+            k, latc = fine.kernels, coarse.lat.as_int64()
+            gen = torch.Generator(device="cuda").manual_seed(1)
+            r, y, t, z = (torch.randn(fine.lat.shape, dtype=dt, device="cuda", generator=gen)
+                          for _ in range(4))
+            rc, zc = (torch.randn(coarse.lat.shape, dtype=dt, device="cuda", generator=gen)
+                      for _ in range(2))
+
+            def cell_restrict():
+                k.axpy(t, -1.0, y, r)
+                rc.zero_()
+                k.restrict(latc, J, t, rc)
+
+            def cell_prolong():
+                k.prolong(latc, J, zc, t)
+                k.axpy(z, 1.0e-3, t, z)
+
+            ms = interleaved({
+                "cell_restrict": cell_restrict,
+                "row_restrict": lambda: k.restrict_row(latc, J, r, y, rc),
+                "cell_prolong": cell_prolong,
+                "row_prolong": lambda: k.prolong_row(latc, J, zc, z, True),
+                "stream_2r1w": lambda: t.add_(y, alpha=-1e-9)})
+            nf, nc_ = fine.lat.ndofs_local, coarse.lat.ndofs_local
+            nbytes = {"restrict": size * (2 * nf + nc_), "prolong": size * (nc_ + 2 * nf),
+                      "stream_2r1w": size * 3 * t.numel()}
+            tbs = {name: nbytes[name.split("_", 1)[1] if name != "stream_2r1w" else name]
+                   / (v["median"] * 1e-3) / 1e12 for name, v in ms.items()}
+            rec["pairs"].append({"float": 8 * size, "pair": [fine.degree, coarse.degree],
+                                 "dofs": [nf, nc_], "ms": ms, "tb_per_s": tbs,
+                                 "speedup": {"restrict": ms["cell_restrict"]["median"]
+                                             / ms["row_restrict"]["median"],
+                                             "prolong": ms["cell_prolong"]["median"]
+                                             / ms["row_prolong"]["median"]}})
+            del r, y, t, z, rc, zc
+        del pbs
+        torch.cuda.empty_cache()
+    return rec
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--degree", type=int, default=3)
@@ -74,6 +171,10 @@ def main(argv=None) -> int:
                     help="a second, tighter tolerance for the pmg variants' solves (0: none)")
     ap.add_argument("--tail", default="",
                     help="comma-separated tail_nodes values: add hpmg_tN (and hpmg32_tN) per value")
+    ap.add_argument("--transfer", default="cell",
+                    help="comma-separated p_transfer values (cell,row): row adds <variant>_row")
+    ap.add_argument("--transfer-kernels", action="store_true",
+                    help="time the row transfer kernels against the launches they replace, and stop")
     ap.add_argument("--no-yardsticks", action="store_true",
                     help="leave out cg_fused and pcg_fused")
     a = ap.parse_args(argv)
@@ -93,13 +194,29 @@ def main(argv=None) -> int:
     tails = [int(t) for t in a.tail.split(",") if t]
     if tails and not a.hlevels:
         raise SystemExit("--tail needs --hlevels (the tail without h-levels is not measured)")
+    transfers = [t for t in a.transfer.split(",") if t]
+    if not transfers or set(transfers) - {"cell", "row"} or "cell" not in transfers:
+        raise SystemExit("--transfer takes cell or cell,row (cell is the yardstick)")
     nx = compute_mesh_size(a.ndofs, a.degree)
+    if a.transfer_kernels:
+        print(json.dumps(transfer_kernels(a, nx)), flush=True)
+        return 0
     pb = PoissonProblem(Comm(), nx, a.degree, 1, False, torch.float64, "gpu", a.perturb, a.kappa)
     b = pb.assemble_rhs()
 
     def make(variant):
         op = make_operator(pb)
-        if variant == "cg_fused":
+        if variant.endswith("_row"):
+            base = variant[:-4]
+            kw = {"p_transfer": "row"}
+            if base.startswith("hpmg"):
+                kw["h_levels"] = a.hlevels
+            if base.split("_t")[0].endswith("32"):
+                kw["cycle_dtype"] = torch.float32
+            if "_t" in base:
+                kw["tail_nodes"] = int(base.partition("_t")[2])
+            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, **kw))
+        elif variant == "cg_fused":
             cg = DeviceCG(pb)
         elif variant == "pcg_fused":
             cg = DeviceCG(pb, "jacobi", loop="fused")
@@ -127,6 +244,8 @@ def main(argv=None) -> int:
         variants += ("pmg32",) + (("hpmg32",) if a.hlevels else ())
     for n in tails:
         variants += (f"hpmg_t{n}",) + ((f"hpmg32_t{n}",) if a.cycle_float == 32 else ())
+    if "row" in transfers:
+        variants += tuple(f"{v}_row" for v in variants if "pmg" in v)
     solves = tuple(v for v in variants if "pmg" in v)
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
@@ -286,12 +405,17 @@ def main(argv=None) -> int:
     if a.tol2 > 0:
         rec["tol2"] = {"tol": a.tol2, "iters": iters2, "true_residual": true_res2,
                        "wall_s": {v: spread(s) for v, s in wall2.items()}}
+    if "row" in transfers:
+        rec["transfer"] = {v: {"info": state[v][1].pmg.info(), "yardstick": v[:-4],
+                               "wall_s": spread(wall[v]) if v in wall else None,
+                               "true_residual": true_res.get(v)}
+                           for v in variants if v.endswith("_row")}
     if tails:
         # per tailed variant: the whole cycle, and the tail's one call against the
         # untailed hierarchy's `_vcycle` from the same level (the launches it replaces)
         rec["tail"] = {}
         for v in variants:
-            if "_t" not in v:
+            if "_t" not in v or v.endswith("_row"):
                 continue
             tp = state[v][1].pmg
             up = state[v.partition("_t")[0]][1].pmg
@@ -356,6 +480,9 @@ def main(argv=None) -> int:
         rec["hpmg_true_residual"] = true_res.get("hpmg")
         rec["hpmg_parts_ms"] = hparts
         hp.close()
+    for v in variants:
+        if v.endswith("_row"):
+            state[v][1].pmg.close()
     pmg.close()
     for op, _, _ in state.values():
         op.close()
