@@ -20,7 +20,9 @@ h-levels under its degree-1 level, -1 = as many as the mesh allows;
 mixed-precision solve; --pmg_tail N: its trailing degree-1 levels of at most
 N nodes run in one kernel launch, one rank only; --pmg_transfer {cell,row}:
 the transfer kernels between its p-levels, row = the row-streaming ones that
-fold the residual and the update),
+fold the residual and the update; --pmg_q1 {matfree,stencil}: the operator
+of its degree-1 levels, stencil = their assembled 27-point stencils streamed,
+with the Chebyshev step fused into the apply on one rank),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -102,6 +104,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Transfer kernels between the p-multigrid's p-levels (--cg --precond "
                          "pmg): cell = per cell; row = by lattice rows, one restriction that "
                          "folds the residual and one prolongation that folds the update")
+    ap.add_argument("--pmg_q1", default="matfree", choices=["matfree", "stencil"],
+                    help="Operator of the p-multigrid's degree-1 levels, h-levels included (--cg "
+                         "--precond pmg): matfree = the matrix-free kernels; stencil = the "
+                         "assembled 27-point stencil, streamed")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -128,6 +134,8 @@ def parse_args(argv=None):
         raise SystemExit("error: Option 'pmg_tail' needs 'cg' and 'precond pmg'")
     if args.pmg_transfer != "cell" and not (args.cg and args.precond == "pmg"):
         raise SystemExit("error: Option 'pmg_transfer' needs 'cg' and 'precond pmg'")
+    if args.pmg_q1 != "matfree" and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_q1' needs 'cg' and 'precond pmg'")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
@@ -242,6 +250,8 @@ def run_benchmark(comm, nx, args, platform):
         pmg_opts["tail_nodes"] = args.pmg_tail
     if args.pmg_transfer != "cell":
         pmg_opts["p_transfer"] = args.pmg_transfer
+    if args.pmg_q1 != "matfree":
+        pmg_opts["q1_operator"] = args.pmg_q1
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,

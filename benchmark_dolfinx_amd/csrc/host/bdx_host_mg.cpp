@@ -311,6 +311,30 @@ void stencil_host(const BdxLattice& lat, const T* S, const T* z, T* y) {
       for (int k = 0; k < L2; ++k) y[lat.idx(i, j, k)] = stencil27_node<T>(lat, S, z, i, j, k);
 }
 
+// Host twin of bdx_stencil27_cheb (csrc/hip/lap_stencil27.h): the same bodies
+// on the owned nodes.
+template <typename T>
+int stencil_cheb_host(const int64_t* latd, const int64_t* own, const T* S, const T* dinv,
+                      const T* r, const T* z_in, T* d, T* z_out, T a, T b) {
+  if (!latd || !own || !S || !dinv || !r || !z_in || !d || !z_out || z_out == z_in) return 1;
+  const BdxLattice lat = BdxLattice::from(latd);
+  if (lat.tsy || lat.P != 1 || lat.ld < lat.L[2] || lat.ld > 0x7fffffffLL) return 1;
+  for (int ax = 0; ax < 3; ++ax)
+    if (lat.L[ax] < 1 || lat.L[ax] > 0x7fffffffLL || lat.L[ax] != lat.n[ax] + 1 || own[ax] < 0 ||
+        own[ax] > lat.L[ax])
+      return 1;
+  const int o0 = static_cast<int>(own[0]), o1 = static_cast<int>(own[1]),
+            o2 = static_cast<int>(own[2]);
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int i = 0; i < o0; ++i)
+    for (int j = 0; j < o1; ++j)
+      for (int k = 0; k < o2; ++k) {
+        const T s = stencil27_node<T>(lat, S, z_in, i, j, k);
+        cheb_entry_fused<T>(true, a, b, dinv, r, s, d, z_in, z_out, lat.idx(i, j, k));
+      }
+  return 0;
+}
+
 template <typename T>
 void tail_smooth_host(const TailLevel<T>& v, bool zero_guess) {
   const BdxLattice& l = v.lat;
@@ -385,6 +409,10 @@ extern "C" {
   }                                                                           \
   void bdx_cpu_stencil27_##SUF BDX_P_CPU_STENCIL27(T) {                       \
     stencil_host<T>(BdxLattice::from(latd), S, z, y);                         \
+  }                                                                           \
+  int bdx_cpu_stencil27_cheb_##SUF BDX_P_CPU_STENCIL27_CHEB(T) {              \
+    return stencil_cheb_host<T>(latd, own, S, dinv, r, z_in, d, z_out,        \
+                                static_cast<T>(a), static_cast<T>(b));        \
   }
 
 BDX_HOST_MG_API(double, f64)

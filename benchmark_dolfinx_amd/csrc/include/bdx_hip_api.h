@@ -319,6 +319,22 @@ BDX_TWINS(int, bdx_prolong_row, BDX_P_PROLONG_ROW)
   T* vc, hipStream_t st)
 BDX_TWINS(int, bdx_restrict_row, BDX_P_RESTRICT_ROW)
 
+// --------------------------------------------------- lap_stencil27_<suf>.hip
+// The assembled 27-point operator S[27][size] of the degree-1 lattice latd
+// (ops/kernels.py: stencil27), streamed: y = S u on every local row, ghost rows
+// included (u forward-exchanged by the caller).  hipErrorInvalidValue, before
+// anything is launched, for a degree other than 1, a tiled descriptor, extents
+// beyond int, a null pointer or y == u.
+#define BDX_P_STENCIL27_APPLY(T) (const int64_t* latd, const T* S, const T* u, T* y, hipStream_t st)
+BDX_TWINS(int, bdx_stencil27_apply, BDX_P_STENCIL27_APPLY)
+// One Chebyshev step in one launch over the own[0] x own[1] x own[2] owned
+// nodes: d = a d + b dinv (r - S z_in); z_out = z_in + d, bit for bit
+// bdx_stencil27_apply into a scratch vector followed by bdx_cheb_step.  Refused
+// like bdx_stencil27_apply, and for z_out == z_in.
+#define BDX_P_STENCIL27_CHEB(T) (const int64_t* latd, const int64_t* own, const T* S, const T* dinv, const T* r, \
+  const T* z_in, T* d, T* z_out, double a, double b, hipStream_t st)
+BDX_TWINS(int, bdx_stencil27_cheb, BDX_P_STENCIL27_CHEB)
+
 // --------------------------------------------------------- pmg_tail_<suf>.hip
 // z = the V-cycle from the first level of the table down and back up, applied
 // to r (the table's other vectors are work space); htab / dtab: the host and

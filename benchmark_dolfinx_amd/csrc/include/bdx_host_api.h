@@ -114,6 +114,13 @@ BDX_HOST_TWINS(int, bdx_cpu_pmg_tail, BDX_P_CPU_PMG_TAIL)
 // tail's operator, alone).
 #define BDX_P_CPU_STENCIL27(T) (const int64_t* latd, const T* S, const T* z, T* y)
 BDX_HOST_TWINS(void, bdx_cpu_stencil27, BDX_P_CPU_STENCIL27)
+// One Chebyshev step over the own[0] x own[1] x own[2] owned nodes with that
+// stencil: d = a d + b dinv (r - S z_in); z_out = z_in + d; the host twin of
+// bdx_stencil27_cheb, nonzero for a descriptor it refuses, a null pointer or
+// z_out == z_in.
+#define BDX_P_CPU_STENCIL27_CHEB(T) (const int64_t* latd, const int64_t* own, const T* S, const T* dinv, \
+  const T* r, const T* z_in, T* d, T* z_out, double a, double b)
+BDX_HOST_TWINS(int, bdx_cpu_stencil27_cheb, BDX_P_CPU_STENCIL27_CHEB)
 // out = (float)a over the owned rows (round to nearest even): the host twin
 // of bdx_demote_f64_f32 (csrc/hip/mixed.hip).
 void bdx_cpu_demote_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,

@@ -11,7 +11,8 @@
 //   p-transfers by rows   the index helpers of lap_rowtransfer.h: cell and
 //                 local index of a fine node, support and weights of a coarse one
 //   stencil27     one row of a level's assembled 27-point operator
-//   cheb_entry    one entry of a Chebyshev-Jacobi step
+//   cheb_entry    one entry of a Chebyshev-Jacobi step (cheb_entry_fused: with
+//                 the operator's value handed over, lap_stencil27.h)
 // and the checks of a level pair of the p- and the h-transfers.
 #pragma once
 #include <cstdint>
@@ -181,11 +182,17 @@ BDX_HD T hrestrict_node(const BdxLattice& lc, const BdxLattice& lf, const HTrans
 // (A z) at node (i, j, k) of a degree-1 lattice (lattice layout, every extent
 // within int) with the assembled stencil S[27][lat.size()], plane (di + 1) 9 +
 // (dj + 1) 3 + (dk + 1): the sum of S[p][n] z[n + offset(p)] over the
-// neighbours inside the lattice, p ascending.  The tail's kernel keeps this
-// loop written out in its own `tail_apply` (pmg_tail.h explains why); both
-// are checked against each other by tests/test_gpu_pmg_tail.py.
-template <typename T>
-BDX_HD T stencil27_node(const BdxLattice& lat, const T* S, const T* z, int i, int j, int k) {
+// neighbours inside the lattice, p ascending.  A neighbour outside the lattice
+// is skipped without a branch: its term is 0 z[n], which leaves the sum as it
+// is, bit for bit, for every finite z[n] (and z[n] is in the sum anyway), and
+// its two loads are the node's own S[p][n] and z[n].  No load waits for a
+// branch that way, and a streaming kernel keeps all 54 in flight.  The tail's kernel
+// keeps this loop written out in its own `tail_apply` (pmg_tail.h explains
+// why); both are checked against each other by tests/test_gpu_pmg_tail.py.
+// SP: how S is read, `const T*` or anything else with its `S[n]`
+// (csrc/hip/lap_stencil27.h chooses the cache policy of S that way).
+template <typename T, typename SP>
+BDX_HD T stencil27_node(const BdxLattice& lat, SP S, const T* z, int i, int j, int k) {
   const int L0 = static_cast<int>(lat.L[0]), L1 = static_cast<int>(lat.L[1]),
             L2 = static_cast<int>(lat.L[2]);
   const int64_t ns = lat.size();
@@ -197,15 +204,15 @@ BDX_HD T stencil27_node(const BdxLattice& lat, const T* S, const T* z, int i, in
     for (int dj = -1; dj <= 1; ++dj)
 #pragma unroll
       for (int dk = -1; dk <= 1; ++dk) {
-        if (i + di < 0 || i + di >= L0 || j + dj < 0 || j + dj >= L1 || k + dk < 0 ||
-            k + dk >= L2)
-          continue;
+        const bool in = i + di >= 0 && i + di < L0 && j + dj >= 0 && j + dj < L1 &&
+                        k + dk >= 0 && k + dk < L2;
         const int64_t p = (di + 1) * 9 + (dj + 1) * 3 + (dk + 1);
-        const int64_t from = lat.idx(i + di, j + dj, k + dk);
+        const int64_t from = in ? lat.idx(i + di, j + dj, k + dk) : at;
         if (BDX_OOB(p * ns + at, 27 * ns, "pmg_tail stencil") ||
             BDX_OOB(from, ns, "pmg_tail apply load"))
           continue;
-        s += S[p * ns + at] * z[from];
+        const T c = S[p * ns + at];
+        s += (in ? c : T(0)) * z[from];
       }
   return s;
 }
@@ -225,4 +232,43 @@ BDX_HD void cheb_entry(bool first, T a, T b, const T* dinv, const T* r, const T*
     d[at] = dn;
     z[at] = z[at] + dn;
   }
+}
+
+// The sum a d + t of a Chebyshev direction, t = b dinv (r - y), with its
+// rounding spelled out: one fused multiply-add (`fused`), or a multiply and an
+// add.  cheb_entry above leaves that choice to the compiler's contraction; a
+// second device kernel that has to reproduce a compiled cheb_entry bit for bit
+// (csrc/hip/lap_stencil27.h says which entries got which) makes it here.  The
+// host build contracts nothing, so both are the plain expression there.
+#if defined(__HIP_DEVICE_COMPILE__)
+// (the empty asm keeps the rounded product out of the contraction's reach)
+BDX_HD double cheb_sum(bool fused, double a, double d, double t) {
+  if (fused) return __builtin_fma(a, d, t);
+  double p = a * d;
+  asm volatile("" : "+v"(p));
+  return p + t;
+}
+BDX_HD float cheb_sum(bool fused, float a, float d, float t) {
+  if (fused) return __builtin_fmaf(a, d, t);
+  float p = a * d;
+  asm volatile("" : "+v"(p));
+  return p + t;
+}
+#else
+template <typename T>
+BDX_HD T cheb_sum(bool, T a, T d, T t) {
+  return a * d + t;
+}
+#endif
+
+// cheb_entry's update with (A z_in)[at] = y handed over as a value and the
+// iterate ping-ponged: d = a d + b dinv (r - y);  z_out = z_in + d (never the
+// first step, which has no operator); `fused`: cheb_sum.
+template <typename T>
+BDX_HD void cheb_entry_fused(bool fused, T a, T b, const T* dinv, const T* r, T y, T* d,
+                             const T* z_in, T* z_out, int64_t at) {
+  const T t = b * dinv[at] * (r[at] - y);
+  const T dn = cheb_sum(fused, a, d[at], t);
+  d[at] = dn;
+  z_out[at] = z_in[at] + dn;
 }

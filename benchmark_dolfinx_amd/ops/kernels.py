@@ -107,6 +107,18 @@ def stencil27(A, lat) -> np.ndarray:
     return S
 
 
+def _stencil27_check(lat, dtype, S, *vecs) -> None:
+    """S is the (27, nstore) stencil of lattice `lat` and `vecs` its lattice
+    vectors, all of `dtype` (the kernels index them by lattice node)."""
+    if S.dtype != dtype or tuple(S.shape) != (27, lat.nstore) or not S.is_contiguous():
+        raise TypeError(f"expected a contiguous {dtype} stencil of shape (27, {lat.nstore}), got "
+                        f"{S.dtype} {tuple(S.shape)}")
+    for v in vecs:
+        if v is not None and (v.dtype != dtype or tuple(v.shape) != tuple(lat.shape)):
+            raise TypeError(f"expected a {dtype} lattice vector of shape {tuple(lat.shape)}, "
+                            f"got {v.dtype} {tuple(v.shape)}")
+
+
 class PmgTail:
     """The device data of the V-cycle tail (csrc/hip/pmg_tail.h): per level of
     `levels` (consecutive degree-1 levels of a `PMultigrid`, the last one its
@@ -173,6 +185,7 @@ class HipKernels:
         self.suf = _suf(dtype)
         self.npart = self.lib.bdx_hip_partials_size()
         self.o = lat.owned_hi
+        self.own = np.asarray(self.o, dtype=np.int64)
 
     def _f(self, name):
         return getattr(self.lib, f"{name}_{self.suf}")
@@ -349,6 +362,23 @@ class HipKernels:
                                         ptr(tab.fpos), ptr(vf), ptr(y), ptr(vc), _stream()),
                "hrestrict")
 
+    def stencil27_apply(self, S, u, y):
+        """y = S u on every local row of this (degree-1) lattice, ghost rows
+        included, with its assembled 27-point stencil S (`stencil27`;
+        lap_stencil27.h).  u is forward-exchanged by the caller."""
+        _stencil27_check(self.lat, self.dtype, S, u, y)
+        _check(self._f("bdx_stencil27_apply")(ptr(self.latd), ptr(S), ptr(u), ptr(y), _stream()),
+               "stencil27_apply")
+
+    def stencil27_cheb(self, S, dinv, r, z_in, d, z_out, a: float, b: float):
+        """One Chebyshev step in one launch over the owned rows: d = a d + b
+        dinv (r - S z_in); z_out = z_in + d (z_out is not z_in); bit for bit
+        `stencil27_apply` followed by `cheb_step`."""
+        _stencil27_check(self.lat, self.dtype, S, dinv, r, z_in, d, z_out)
+        _check(self._f("bdx_stencil27_cheb")(ptr(self.latd), ptr(self.own), ptr(S), ptr(dinv),
+                                             ptr(r), ptr(z_in), ptr(d), ptr(z_out), float(a),
+                                             float(b), _stream()), "stencil27_cheb")
+
     def pmg_tail(self, tail: PmgTail, r, z):
         """z = the V-cycle of the tail's levels applied to r, in one launch of
         one workgroup (pmg_tail.h); r, z: vectors of its first level."""
@@ -413,8 +443,10 @@ class HostKernels:
         self.lib = native.host()
         self.lat = lat
         self.latd = lat.as_int64()
+        self.dtype = dtype
         self.suf = _suf(dtype)
         self.o = lat.owned_hi
+        self.own = np.asarray(self.o, dtype=np.int64)
 
     def _f(self, name):
         return getattr(self.lib, f"{name}_{self.suf}")
@@ -462,6 +494,20 @@ class HostKernels:
     def stencil27(self, S, z, y):
         """y = A z with the 27-point stencil S of this (degree-1) lattice."""
         self._f("bdx_cpu_stencil27")(ptr(self.latd), ptr(S), ptr(z), ptr(y))
+
+    def stencil27_apply(self, S, u, y):
+        """`HipKernels.stencil27_apply` on the host twin (`stencil27`, checked)."""
+        _stencil27_check(self.lat, self.dtype, S, u, y)
+        if self.lat.degree != 1 or u is y:
+            raise ValueError("stencil27_apply: not a degree-1 lattice, or y is u")
+        self.stencil27(S, u, y)
+
+    def stencil27_cheb(self, S, dinv, r, z_in, d, z_out, a: float, b: float):
+        _stencil27_check(self.lat, self.dtype, S, dinv, r, z_in, d, z_out)
+        if self._f("bdx_cpu_stencil27_cheb")(ptr(self.latd), ptr(self.own), ptr(S), ptr(dinv),
+                                             ptr(r), ptr(z_in), ptr(d), ptr(z_out), float(a),
+                                             float(b)):
+            raise ValueError("stencil27_cheb: not a degree-1 lattice, or z_out is z_in")
 
     def _rows(self, a, da, out, do):
         for v, dt in ((a, da), (out, do)):

@@ -62,6 +62,22 @@ h-transfers' modes, so a p-pair runs the h-pair's branch of the cycle: one
 restriction that folds the residual and one prolongation that folds the
 update, with no axpy, no zeroing and no colour launches.  The operators are
 those of the cell kernels in another summation order.
+
+Stencil levels (`q1_operator="stencil"`, off by default): every degree-1
+level outside the tail (the degree-1 p-level, the h-levels, level 0 of a
+degree-1 problem) applies its assembled 27-point stencil `lv.S`
+(`ops.kernels.stencil27` of `CSROperator`, as in the tail) with the streaming
+kernels of csrc/hip/lap_stencil27.h instead of the matrix-free operator, which
+it equals to rounding.  Setup is unchanged: the power iteration runs on
+`lv.op`, so lambda_max and every coefficient are those of the default.  On one
+rank a Chebyshev step is one launch, `stencil27_cheb`, that never stores A z
+and ping-pongs the iterate between `z` and the level's `t` (free on degree-1
+levels: the h-pair branch of the cycle does not use it); the first step from a
+zero guess writes the buffer from which the last step lands in `z`, and only
+an odd number of steps from a nonzero guess ends with a copy.  On more ranks S
+holds the rank's own cells, a ghost row its partial sums, so a step keeps
+`CSROperator.apply`'s protocol: forward exchange, `stencil27_apply` on every
+local row, reverse exchange, `cheb_step`.
 """
 
 from __future__ import annotations
@@ -117,6 +133,7 @@ class _Level:
         self.z = None               # coarse levels: the correction
         self.J = None               # p-transfer table to the next coarser level
         self.H = None               # or the h-transfer tables to it
+        self.S = None               # q1_operator="stencil": the 27-point stencil
         self.coef = []
         self.lambda_max = 0.0
 
@@ -144,14 +161,18 @@ class PMultigrid:
 
     p_transfer: "cell" = the per-cell transfer kernels between the p-levels;
     "row" = the row-streaming ones (module docstring), which accept `add` and
-    `y` in `prolong` / `restrict` as the h-pairs do."""
+    `y` in `prolong` / `restrict` as the h-pairs do.
+
+    q1_operator: "matfree" = every level applies its matrix-free operator;
+    "stencil" = the degree-1 levels outside the tail apply their assembled
+    27-point stencil `lv.S` (module docstring)."""
 
     TAIL_MAX_NODES = CONSTANTS["kTailMaxNodes"]
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
                  h_levels: int = 0, cycle_dtype: torch.dtype | None = None, tail_nodes: int = 0,
-                 p_transfer: str = "cell"):
+                 p_transfer: str = "cell", q1_operator: str = "matfree"):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
@@ -168,6 +189,9 @@ class PMultigrid:
         if p_transfer not in ("cell", "row"):
             raise ValueError(f"p_transfer must be 'cell' or 'row', got {p_transfer!r}")
         self.p_transfer = p_transfer
+        if q1_operator not in ("matfree", "stencil"):
+            raise ValueError(f"q1_operator must be 'matfree' or 'stencil', got {q1_operator!r}")
+        self.q1_operator = q1_operator
         if cycle_dtype is None:
             cycle_dtype = pb.dtype
         if cycle_dtype not in (torch.float32, torch.float64) or \
@@ -234,6 +258,14 @@ class PMultigrid:
                 from ..ops.kernels import PmgTail
                 self.tail_start, self.tail_levels = start, len(self.levels) - start
                 self.tail = PmgTail(self.levels[start:], cycle_dtype, pb.device)
+        # the stencils of the degree-1 levels above the tail
+        if self.q1_operator == "stencil":
+            from ..models.poisson import CSROperator
+            from ..ops.kernels import stencil27
+            end = len(self.levels) if self.tail_start is None else self.tail_start
+            for lv in self.levels[:end]:
+                if lv.pb.degree == 1:
+                    lv.S = torch.from_numpy(stencil27(CSROperator(lv.pb), lv.pb.lat)).to(pb.device)
 
     # ---------------------------------------------------------------- setup
     @staticmethod
@@ -299,7 +331,46 @@ class PMultigrid:
 
     # ---------------------------------------------------------------- cycle
     @staticmethod
+    def _apply(lv: _Level, z: torch.Tensor, y: torch.Tensor) -> None:
+        """y = A z on the owned rows of level lv."""
+        if lv.S is None:
+            lv.op.apply(z, y)
+            return
+        lv.pb.halo.forward(z)
+        lv.k.stencil27_apply(lv.S, z, y)
+        lv.pb.halo.reverse(y)
+
+    @staticmethod
+    def _smooth_stencil(lv: _Level, r: torch.Tensor, z: torch.Tensor, zero_guess: bool) -> None:
+        """`_smooth` on a stencil level."""
+        if lv.pb.halo.active:
+            for i, (a, b) in enumerate(lv.coef):
+                if i == 0 and zero_guess:
+                    lv.k.cheb_step(True, 0.0, b, lv.dinv, r, None, lv.d, z)
+                else:
+                    PMultigrid._apply(lv, z, lv.y)
+                    lv.k.cheb_step(False, a, b, lv.dinv, r, lv.y, lv.d, z)
+            return
+        # one rank: every step with an operator reads `cur` and writes the
+        # other of z and t; the first step of a zero guess has none and writes
+        # the buffer from which the others end in z
+        fused = len(lv.coef) - (1 if zero_guess else 0)
+        cur = lv.t if zero_guess and fused % 2 else z
+        for i, (a, b) in enumerate(lv.coef):
+            if i == 0 and zero_guess:
+                lv.k.cheb_step(True, 0.0, b, lv.dinv, r, None, lv.d, cur)
+                continue
+            nxt = lv.t if cur is z else z
+            lv.k.stencil27_cheb(lv.S, lv.dinv, r, cur, lv.d, nxt, a, b)
+            cur = nxt
+        if cur is not z:        # an odd number of steps from a nonzero guess
+            z.copy_(cur)
+
+    @staticmethod
     def _smooth(lv: _Level, r: torch.Tensor, z: torch.Tensor, zero_guess: bool) -> None:
+        if lv.S is not None:
+            PMultigrid._smooth_stencil(lv, r, z, zero_guess)
+            return
         for i, (a, b) in enumerate(lv.coef):
             if i == 0 and zero_guess:
                 lv.k.cheb_step(True, 0.0, b, lv.dinv, r, None, lv.d, z)
@@ -316,7 +387,7 @@ class PMultigrid:
         if l == len(self.levels) - 1:
             return
         nxt = self.levels[l + 1]
-        lv.op.apply(z, lv.y)
+        self._apply(lv, z, lv.y)
         if lv.H is not None or self.p_transfer == "row":
             # h-pair, or a p-pair by rows: the residual and the correction's
             # sum are folded into the transfer kernels' load and store
@@ -360,6 +431,8 @@ class PMultigrid:
             out["tail_levels"] = self.tail_levels
         if self.p_transfer != "cell":
             out["p_transfer"] = self.p_transfer
+        if self.q1_operator != "matfree":
+            out["q1_operator"] = self.q1_operator
         return out
 
     def close(self) -> None:

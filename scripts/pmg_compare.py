@@ -13,6 +13,8 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
                                                              (row transfers, profiles/pmg_rowtransfer.md)
   python scripts/pmg_compare.py --degree 6 --transfer-kernels
                                                              (their kernels against the launches they replace)
+  python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --q1 matfree,stencil --no-yardsticks
+                                                             (stencil levels, profiles/pmg_q1stencil.md)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -35,6 +37,16 @@ its own auto-selected operator:
   <v>_row    (--transfer cell,row) every pmg variant v again with PMultigrid(p_transfer="row"):
              the row-streaming transfers between the p-levels (csrc/hip/lap_rowtransfer.h);
              interleaved like hpmg, so the yardstick of v_row is v in the same process
+
+  <v>_s27    (--q1 matfree,stencil) every pmg variant v again with PMultigrid(q1_operator=
+             "stencil"): the degree-1 levels on their assembled 27-point stencils
+             (csrc/hip/lap_stencil27.h); interleaved like hpmg, the yardstick of v_s27 is v.  The
+             "q1" block also times, per variant pair, the first degree-1 level and everything
+             below it alone, both ways, the construction of the two hierarchies (the difference is
+             the host CSR assembly of the stencils plus their upload) and, per stencil level,
+             `stencil27_apply` and `stencil27_cheb` against the matrix-free apply and apply +
+             `cheb_step` they replace, with the effective TB/s over S and the vectors (apply:
+             27 + 2 values per node, fused step: 27 + 6)
 
 --transfer-kernels: no solve.  For every p-pair of the configured problem, in FP64 and FP32
 vectors, device-event times (the median of --reps batches of five calls, the candidates
@@ -173,6 +185,9 @@ def main(argv=None) -> int:
                     help="comma-separated tail_nodes values: add hpmg_tN (and hpmg32_tN) per value")
     ap.add_argument("--transfer", default="cell",
                     help="comma-separated p_transfer values (cell,row): row adds <variant>_row")
+    ap.add_argument("--q1", default="matfree",
+                    help="comma-separated q1_operator values (matfree,stencil): stencil adds "
+                         "<variant>_s27")
     ap.add_argument("--transfer-kernels", action="store_true",
                     help="time the row transfer kernels against the launches they replace, and stop")
     ap.add_argument("--no-yardsticks", action="store_true",
@@ -197,6 +212,9 @@ def main(argv=None) -> int:
     transfers = [t for t in a.transfer.split(",") if t]
     if not transfers or set(transfers) - {"cell", "row"} or "cell" not in transfers:
         raise SystemExit("--transfer takes cell or cell,row (cell is the yardstick)")
+    q1s = [t for t in a.q1.split(",") if t]
+    if not q1s or set(q1s) - {"matfree", "stencil"} or "matfree" not in q1s:
+        raise SystemExit("--q1 takes matfree or matfree,stencil (matfree is the yardstick)")
     nx = compute_mesh_size(a.ndofs, a.degree)
     if a.transfer_kernels:
         print(json.dumps(transfer_kernels(a, nx)), flush=True)
@@ -204,36 +222,36 @@ def main(argv=None) -> int:
     pb = PoissonProblem(Comm(), nx, a.degree, 1, False, torch.float64, "gpu", a.perturb, a.kappa)
     b = pb.assemble_rhs()
 
+    def pmg_kwargs(variant):
+        """The PMultigrid options a variant's name spells: [h]pmg[32][_tN][_row][_s27]."""
+        kw = {}
+        if variant.endswith("_s27"):
+            kw["q1_operator"], variant = "stencil", variant[:-4]
+        if variant.endswith("_row"):
+            kw["p_transfer"], variant = "row", variant[:-4]
+        base, _, n = variant.partition("_t")
+        if n:
+            kw["tail_nodes"] = int(n)
+        if base.startswith("hpmg"):
+            kw["h_levels"] = a.hlevels
+        if base.endswith("32"):
+            kw["cycle_dtype"] = torch.float32
+        return kw
+
+    build_s = {}
+
     def make(variant):
         op = make_operator(pb)
-        if variant.endswith("_row"):
-            base = variant[:-4]
-            kw = {"p_transfer": "row"}
-            if base.startswith("hpmg"):
-                kw["h_levels"] = a.hlevels
-            if base.split("_t")[0].endswith("32"):
-                kw["cycle_dtype"] = torch.float32
-            if "_t" in base:
-                kw["tail_nodes"] = int(base.partition("_t")[2])
-            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, **kw))
-        elif variant == "cg_fused":
+        if variant == "cg_fused":
             cg = DeviceCG(pb)
         elif variant == "pcg_fused":
             cg = DeviceCG(pb, "jacobi", loop="fused")
-        elif variant == "hpmg":
-            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels))
-        elif variant == "pmg32":
-            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, cycle_dtype=torch.float32))
-        elif variant == "hpmg32":
-            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(pb, h_levels=a.hlevels,
-                                                    cycle_dtype=torch.float32))
-        elif "_t" in variant:
-            base, _, n = variant.partition("_t")
-            cg = DeviceCG(pb, "pmg", pmg=PMultigrid(
-                pb, h_levels=a.hlevels, tail_nodes=int(n),
-                cycle_dtype=torch.float32 if base == "hpmg32" else None))
         else:
-            cg = DeviceCG(pb, "pmg")
+            t0 = time.perf_counter()
+            hierarchy = PMultigrid(pb, **pmg_kwargs(variant))
+            torch.cuda.synchronize()
+            build_s[variant] = time.perf_counter() - t0
+            cg = DeviceCG(pb, "pmg", pmg=hierarchy)
         x = pb.new_vector()
         cg.start(op, x, b)
         return op, cg, x
@@ -246,6 +264,8 @@ def main(argv=None) -> int:
         variants += (f"hpmg_t{n}",) + ((f"hpmg32_t{n}",) if a.cycle_float == 32 else ())
     if "row" in transfers:
         variants += tuple(f"{v}_row" for v in variants if "pmg" in v)
+    if "stencil" in q1s:
+        variants += tuple(f"{v}_s27" for v in variants if "pmg" in v)
     solves = tuple(v for v in variants if "pmg" in v)
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
@@ -410,12 +430,53 @@ def main(argv=None) -> int:
                                "wall_s": spread(wall[v]) if v in wall else None,
                                "true_residual": true_res.get(v)}
                            for v in variants if v.endswith("_row")}
+    if "stencil" in q1s:
+        rec["q1"] = {}
+        for v in variants:
+            if not v.endswith("_s27"):
+                continue
+            sp, mp = state[v][1].pmg, state[v[:-4]][1].pmg
+            i1 = next(i for i, lv in enumerate(sp.levels) if lv.pb.degree == 1)
+            blk = {"info": sp.info(), "yardstick": v[:-4],
+                   "wall_s": spread(wall[v]) if v in wall else None,
+                   "true_residual": true_res.get(v),
+                   "build_s": {"matfree": build_s[v[:-4]], "stencil": build_s[v]},
+                   "level_nodes": [int(lv.pb.lat.L[0] * lv.pb.lat.L[1] * lv.pb.lat.L[2])
+                                   for lv in sp.levels],
+                   "stencil_bytes": [int(lv.S.numel() * lv.S.element_size()) if lv.S is not None
+                                     else 0 for lv in sp.levels]}
+            if i1 > 0:
+                s1, m1 = sp.levels[i1], mp.levels[i1]
+                blk["degree1_and_below_ms"] = {
+                    "matfree": timed(lambda: mp._vcycle(i1, m1.r, m1.z)),
+                    "stencil": timed(lambda: sp._vcycle(i1, s1.r, s1.z))}
+            blk["levels"] = []
+            for sl, ml in zip(sp.levels, mp.levels):
+                if sl.S is None or sl.r is None:
+                    continue
+                ca, cb = sl.coef[-1]
+                size, n = sl.S.element_size(), int(sl.pb.lat.ndofs_local)
+
+                def composed():
+                    ml.op.apply(ml.z, ml.y)
+                    ml.k.cheb_step(False, ca, cb, ml.dinv, ml.r, ml.y, ml.d, ml.z)
+
+                t = {"matfree_apply": timed(lambda: ml.op.apply(ml.z, ml.y)),
+                     "stencil27_apply": timed(lambda: sl.k.stencil27_apply(sl.S, sl.z, sl.y)),
+                     "matfree_apply_cheb_step": timed(composed),
+                     "stencil27_cheb": timed(lambda: sl.k.stencil27_cheb(
+                         sl.S, sl.dinv, sl.r, sl.z, sl.d, sl.t, ca, cb))}
+                blk["levels"].append({
+                    "nodes": n, "float": 8 * size, "ms": t,
+                    "tb_per_s": {"stencil27_apply": 29 * n * size / (t["stencil27_apply"] * 1e-3) / 1e12,
+                                 "stencil27_cheb": 33 * n * size / (t["stencil27_cheb"] * 1e-3) / 1e12}})
+            rec["q1"][v] = blk
     if tails:
         # per tailed variant: the whole cycle, and the tail's one call against the
         # untailed hierarchy's `_vcycle` from the same level (the launches it replaces)
         rec["tail"] = {}
         for v in variants:
-            if "_t" not in v or v.endswith("_row"):
+            if "_t" not in v or v.endswith("_row") or v.endswith("_s27"):
                 continue
             tp = state[v][1].pmg
             up = state[v.partition("_t")[0]][1].pmg
@@ -481,7 +542,7 @@ def main(argv=None) -> int:
         rec["hpmg_parts_ms"] = hparts
         hp.close()
     for v in variants:
-        if v.endswith("_row"):
+        if v.endswith("_row") or v.endswith("_s27"):
             state[v][1].pmg.close()
     pmg.close()
     for op, _, _ in state.values():
