@@ -22,7 +22,9 @@ N nodes run in one kernel launch, one rank only; --pmg_transfer {cell,row}:
 the transfer kernels between its p-levels, row = the row-streaming ones that
 fold the residual and the update; --pmg_q1 {matfree,stencil}: the operator
 of its degree-1 levels, stencil = their assembled 27-point stencils streamed,
-with the Chebyshev step fused into the apply on one rank),
+with the Chebyshev step fused into the apply on one rank; --pmg_q1_assembly
+{csr,direct}: how those stencils and the tail's are built, direct = by the
+assembly kernel on the device instead of the host's CSR matrix),
 --pcg_loop {generic,fused} (with --cg --precond jacobi on the GPU: the generic
 device loop, or the fused operators' CG fusion and native runtime).
 The JSON gains an additive "mi355x" object; the reference keys are
@@ -108,6 +110,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Operator of the p-multigrid's degree-1 levels, h-levels included (--cg "
                          "--precond pmg): matfree = the matrix-free kernels; stencil = the "
                          "assembled 27-point stencil, streamed")
+    ap.add_argument("--pmg_q1_assembly", default="csr", choices=["csr", "direct"],
+                    help="How the 27-point stencils of --pmg_q1 stencil and --pmg_tail are built "
+                         "(--cg --precond pmg): csr = from the host's assembled matrix; direct = "
+                         "by the assembly kernel on the problem's device, no matrix")
     ap.add_argument("--pcg_loop", default="generic", choices=["generic", "fused"],
                     help="Loop of the preconditioned CG (needs --cg --precond jacobi): generic = "
                          "operator apply + vector kernels; fused = the fused operators' CG "
@@ -136,6 +142,10 @@ def parse_args(argv=None):
         raise SystemExit("error: Option 'pmg_transfer' needs 'cg' and 'precond pmg'")
     if args.pmg_q1 != "matfree" and not (args.cg and args.precond == "pmg"):
         raise SystemExit("error: Option 'pmg_q1' needs 'cg' and 'precond pmg'")
+    if args.pmg_q1_assembly != "csr" and not (args.cg and args.precond == "pmg"):
+        raise SystemExit("error: Option 'pmg_q1_assembly' needs 'cg' and 'precond pmg'")
+    if args.pmg_q1_assembly != "csr" and args.pmg_q1 == "matfree" and args.pmg_tail == 0:
+        raise SystemExit("error: Option 'pmg_q1_assembly' needs 'pmg_q1 stencil' or 'pmg_tail'")
     if args.precond != "none" and not args.cg:
         raise SystemExit("error: Option 'precond' needs 'cg'")
     if args.pmg_smooth < 1 or args.pmg_coarse < 1:
@@ -252,6 +262,8 @@ def run_benchmark(comm, nx, args, platform):
         pmg_opts["p_transfer"] = args.pmg_transfer
     if args.pmg_q1 != "matfree":
         pmg_opts["q1_operator"] = args.pmg_q1
+    if args.pmg_q1_assembly != "csr":
+        pmg_opts["q1_assembly"] = args.pmg_q1_assembly
     res = laplace_action(pb, args.nreps, args.cg, args.mat_comp, kernel=args.kernel,
                          geometry=args.geometry, warmup=args.warmup, precond=args.precond,
                          pcg_loop=args.pcg_loop,

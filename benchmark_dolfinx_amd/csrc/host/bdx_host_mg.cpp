@@ -335,6 +335,34 @@ int stencil_cheb_host(const int64_t* latd, const int64_t* own, const T* S, const
   return 0;
 }
 
+// Host twin of bdx_stencil27_assemble (csrc/hip/lap_stencil27_assemble.h):
+// stencil27_assemble_node on every node of the storage, padding included.
+template <typename T>
+int stencil_assemble_host(const int64_t* latd, int nq, const double* phi0, const double* dphi1,
+                          const double* wts, const double* qpts, const T* xv, T kappa,
+                          const T* kc, T* S) {
+  if (!latd || !phi0 || !dphi1 || !wts || !qpts || !xv || !S || nq < 2 || nq > kStencil27MaxNq)
+    return 1;
+  const BdxLattice lat = BdxLattice::from(latd);
+  if (lat.tsy || lat.P != 1 || lat.ld < lat.L[2] || lat.ld > 0x7fffffffLL) return 1;
+  for (int ax = 0; ax < 3; ++ax)
+    if (lat.L[ax] < 1 || lat.L[ax] > 0x7fffffffLL || lat.L[ax] != lat.n[ax] + 1) return 1;
+  const Stencil27Tables<T> tb = stencil27_tables<T>(nq, phi0, dphi1, wts, qpts);
+  const int L0 = static_cast<int>(lat.L[0]), L1 = static_cast<int>(lat.L[1]),
+            ld = static_cast<int>(lat.ld);
+  const int64_t ns = lat.size();
+#pragma omp parallel for collapse(2) schedule(static)
+  for (int i = 0; i < L0; ++i)
+    for (int j = 0; j < L1; ++j)
+      for (int k = 0; k < ld; ++k) {
+        T acc[27];
+        stencil27_assemble_node<T>(lat, tb, xv, kappa, kc, i, j, k, acc);
+        const int64_t at = lat.idx(i, j, k);
+        for (int p = 0; p < 27; ++p) S[p * ns + at] = acc[p];
+      }
+  return 0;
+}
+
 template <typename T>
 void tail_smooth_host(const TailLevel<T>& v, bool zero_guess) {
   const BdxLattice& l = v.lat;
@@ -413,6 +441,10 @@ extern "C" {
   int bdx_cpu_stencil27_cheb_##SUF BDX_P_CPU_STENCIL27_CHEB(T) {              \
     return stencil_cheb_host<T>(latd, own, S, dinv, r, z_in, d, z_out,        \
                                 static_cast<T>(a), static_cast<T>(b));        \
+  }                                                                           \
+  int bdx_cpu_stencil27_assemble_##SUF BDX_P_CPU_STENCIL27_ASSEMBLE(T) {      \
+    return stencil_assemble_host<T>(latd, nq, phi0, dphi1, wts, qpts, xv,     \
+                                    static_cast<T>(kappa), kc, S);            \
   }
 
 BDX_HOST_MG_API(double, f64)

@@ -335,6 +335,18 @@ BDX_TWINS(int, bdx_stencil27_apply, BDX_P_STENCIL27_APPLY)
   const T* z_in, T* d, T* z_out, double a, double b, hipStream_t st)
 BDX_TWINS(int, bdx_stencil27_cheb, BDX_P_STENCIL27_CHEB)
 
+// ------------------------------------------ lap_stencil27_assemble_<suf>.hip
+// That stencil assembled on the device: all of S[27][size] written, nothing
+// zeroed by the caller, from the vertices xv, kappa (kc: per cell, or null)
+// and the tables of bdx_diag (Dd = dphi1 phi0, nq 2 or 3); the rows are those
+// of ops/kernels.py: stencil27 on the rank's assembled matrix, a ghost-plane
+// row holding the rank's partial sums.  hipErrorInvalidValue, before anything
+// is launched, for a descriptor bdx_stencil27_apply refuses, another nq or a
+// null latd, table, xv or S.
+#define BDX_P_STENCIL27_ASSEMBLE(T) (const int64_t* latd, int nq, const double* phi0, const double* dphi1, \
+  const double* wts, const double* qpts, const T* xv, double kappa, const T* kc, T* S, hipStream_t st)
+BDX_TWINS(int, bdx_stencil27_assemble, BDX_P_STENCIL27_ASSEMBLE)
+
 // --------------------------------------------------------- pmg_tail_<suf>.hip
 // z = the V-cycle from the first level of the table down and back up, applied
 // to r (the table's other vectors are work space); htab / dtab: the host and

@@ -121,6 +121,12 @@ BDX_HOST_TWINS(void, bdx_cpu_stencil27, BDX_P_CPU_STENCIL27)
 #define BDX_P_CPU_STENCIL27_CHEB(T) (const int64_t* latd, const int64_t* own, const T* S, const T* dinv, \
   const T* r, const T* z_in, T* d, T* z_out, double a, double b)
 BDX_HOST_TWINS(int, bdx_cpu_stencil27_cheb, BDX_P_CPU_STENCIL27_CHEB)
+// That stencil assembled from the vertices, kappa and the FP64 tables: the
+// host twin of bdx_stencil27_assemble with its arguments, nonzero where that
+// refuses.
+#define BDX_P_CPU_STENCIL27_ASSEMBLE(T) (const int64_t* latd, int nq, const double* phi0, const double* dphi1, \
+  const double* wts, const double* qpts, const T* xv, double kappa, const T* kc, T* S)
+BDX_HOST_TWINS(int, bdx_cpu_stencil27_assemble, BDX_P_CPU_STENCIL27_ASSEMBLE)
 // out = (float)a over the owned rows (round to nearest even): the host twin
 // of bdx_demote_f64_f32 (csrc/hip/mixed.hip).
 void bdx_cpu_demote_f64_f32(int64_t L1, int64_t ld, int64_t o0, int64_t o1, int64_t o2,

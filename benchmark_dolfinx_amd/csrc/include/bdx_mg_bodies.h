@@ -10,7 +10,8 @@
 //                 lattices and its transpose (tables: lap_htransfer.h)
 //   p-transfers by rows   the index helpers of lap_rowtransfer.h: cell and
 //                 local index of a fine node, support and weights of a coarse one
-//   stencil27     one row of a level's assembled 27-point operator
+//   stencil27     one row of a level's assembled 27-point operator, applied
+//                 (stencil27_node) and assembled (stencil27_assemble_node)
 //   cheb_entry    one entry of a Chebyshev-Jacobi step (cheb_entry_fused: with
 //                 the operator's value handed over, lap_stencil27.h)
 // and the checks of a level pair of the p- and the h-transfers.
@@ -18,6 +19,7 @@
 #include <cstdint>
 
 #include "bdx_debug.h"
+#include "bdx_geometry.h"
 #include "bdx_lattice.h"
 
 // p-transfers: both descriptors in the lattice layout, on the same cells and
@@ -215,6 +217,152 @@ BDX_HD T stencil27_node(const BdxLattice& lat, SP S, const T* z, int i, int j, i
         s += (in ? c : T(0)) * z[from];
       }
   return s;
+}
+
+// Assembly of that stencil.
+//
+// The 1D tables of a degree-1 level in T: B = phi0 and Dd = dphi1 phi0 (both
+// nq x 2), the quadrature weights and points; nq is 2 or 3.
+constexpr int kStencil27MaxNq = 3;
+template <typename T>
+struct Stencil27Tables {
+  T B[kStencil27MaxNq * 2];
+  T Dd[kStencil27MaxNq * 2];
+  T wts[kStencil27MaxNq];
+  T qpts[kStencil27MaxNq];
+  int nq;
+};
+
+// From the FP64 tables of a launcher (bdx_diag's arguments), on the host.
+template <typename T>
+inline Stencil27Tables<T> stencil27_tables(int nq, const double* phi0, const double* dphi1,
+                                           const double* wts, const double* qpts) {
+  Stencil27Tables<T> t{};
+  t.nq = nq;
+  for (int q = 0; q < nq; ++q) {
+    for (int a = 0; a < 2; ++a) {
+      t.B[q * 2 + a] = static_cast<T>(phi0[q * 2 + a]);
+      T acc = 0;
+      for (int m = 0; m < nq; ++m)
+        acc += static_cast<T>(dphi1[q * nq + m]) * static_cast<T>(phi0[m * 2 + a]);
+      t.Dd[q * 2 + a] = acc;
+    }
+    t.wts[q] = static_cast<T>(wts[q]);
+    t.qpts[q] = static_cast<T>(qpts[q]);
+  }
+  return t;
+}
+
+// acc += row (AI, AJ, AK) of the element matrix of the local cell (i - AI,
+// j - AJ, k - AK), the cell that has node (i, j, k) as that corner:
+//   Ke[a][b] = kappa_c sum_q grad phi_b . G_q grad phi_a   (G_q symmetric)
+// over the tensor quadrature points, x outermost, with grad phi = (Dd B B,
+// B Dd B, B B Dd) and G_q = trilinear_G with the weight w_x w_y w_z.  Entry b
+// goes to the plane of the neighbour (b - a), a compile-time index: the 27
+// sums stay in registers.  The quadrature loops stay rolled (eight corners x
+// nq^3 points unrolled would be some 10^5 instructions).  A cell outside the
+// lattice in x or y adds nothing (the same answer for every z of the row); one
+// outside in z is computed on the nearest cell of the column with the weight
+// kappa_c = 0, so the lanes of a wave do not diverge.
+template <typename T, int AI, int AJ, int AK>
+BDX_HD void stencil27_assemble_cell(const BdxLattice& lat, const Stencil27Tables<T>& tb,
+                                    const T* xv, T kappa, const T* kc, int i, int j, int k,
+                                    T (&acc)[27]) {
+  const int64_t cx = i - AI, cy = j - AJ;
+  if (cx < 0 || cx >= lat.n[0] || cy < 0 || cy >= lat.n[1] || lat.n[2] < 1) return;
+  int64_t cz = k - AK;
+  const bool has = cz >= 0 && cz < lat.n[2];
+  cz = cz < 0 ? 0 : (cz > lat.n[2] - 1 ? lat.n[2] - 1 : cz);
+  const int64_t nvert = (lat.n[0] + 1) * (lat.n[1] + 1) * (lat.n[2] + 1);
+  (void)nvert;  // read by the BDX_DEBUG index checks only
+  T X[8][3];
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const int64_t at = lat.vidx(cx + (v >> 2), cy + ((v >> 1) & 1), cz + (v & 1));
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      X[v][c] = BDX_OOB(3 * at + c, 3 * nvert, "stencil27 assemble vertex") ? T(0) : xv[3 * at + c];
+  }
+  const int64_t cell = (cx * lat.n[1] + cy) * lat.n[2] + cz;
+  T kap = kappa;
+  if (kc && !BDX_OOB(cell, lat.n[0] * lat.n[1] * lat.n[2], "stencil27 assemble kappa"))
+    kap = kc[cell];
+  if (!has) kap = 0;
+  const int nq = tb.nq;
+#pragma unroll 1
+  for (int qx = 0; qx < nq; ++qx)
+#pragma unroll 1
+    for (int qy = 0; qy < nq; ++qy)
+#pragma unroll 1
+      for (int qz = 0; qz < nq; ++qz) {
+        T G[6];
+        trilinear_G<T>(X, tb.qpts[qx], tb.qpts[qy], tb.qpts[qz],
+                       tb.wts[qx] * tb.wts[qy] * tb.wts[qz], G);
+        const T bx[2] = {tb.B[2 * qx], tb.B[2 * qx + 1]}, dx[2] = {tb.Dd[2 * qx], tb.Dd[2 * qx + 1]};
+        const T by[2] = {tb.B[2 * qy], tb.B[2 * qy + 1]}, dy[2] = {tb.Dd[2 * qy], tb.Dd[2 * qy + 1]};
+        const T bz[2] = {tb.B[2 * qz], tb.B[2 * qz + 1]}, dz[2] = {tb.Dd[2 * qz], tb.Dd[2 * qz + 1]};
+        // kappa G grad phi_a
+        const T g0 = dx[AI] * by[AJ] * bz[AK], g1 = bx[AI] * dy[AJ] * bz[AK],
+                g2 = bx[AI] * by[AJ] * dz[AK];
+        const T t0 = kap * (G[0] * g0 + G[1] * g1 + G[2] * g2);
+        const T t1 = kap * (G[1] * g0 + G[3] * g1 + G[4] * g2);
+        const T t2 = kap * (G[2] * g0 + G[4] * g1 + G[5] * g2);
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+          for (int bj = 0; bj < 2; ++bj)
+#pragma unroll
+            for (int bk = 0; bk < 2; ++bk) {
+              const T h0 = dx[bi] * by[bj] * bz[bk], h1 = bx[bi] * dy[bj] * bz[bk],
+                      h2 = bx[bi] * by[bj] * dz[bk];
+              acc[(bi - AI + 1) * 9 + (bj - AJ + 1) * 3 + (bk - AK + 1)] +=
+                  h0 * t0 + h1 * t1 + h2 * t2;
+            }
+      }
+}
+
+// Row (i, j, k), k < lat.ld, of the assembled operator of a degree-1 lattice
+// (stencil27_lattice_ok) in the 27 planes of stencil27_node: what
+// ops/kernels.py: stencil27 makes of the rank's assembled matrix (csr_build,
+// csrc/host/bdx_host.cpp).
+//   a row of the storage padding (k >= L[2])   0
+//   a Dirichlet row   0, and 1 in the centre where the node is owned
+//   any other row     the rows of the node in the element matrices of the at
+//                     most 8 local cells around it (a ghost-plane row: this
+//                     rank's partial sums), cells in the order of their corner
+//                     (0,0,0), (0,0,1), ... (1,1,1); then 0 in every Dirichlet
+//                     column and for every neighbour outside the local lattice.
+// Every plane is written; the order of cells, points and terms is fixed, so
+// the row is the same on every run.
+template <typename T>
+BDX_HD void stencil27_assemble_node(const BdxLattice& lat, const Stencil27Tables<T>& tb,
+                                    const T* xv, T kappa, const T* kc, int i, int j, int k,
+                                    T (&acc)[27]) {
+#pragma unroll
+  for (int p = 0; p < 27; ++p) acc[p] = 0;
+  if (k >= lat.L[2]) return;
+  if (lat.is_bc(i, j, k)) {
+    if (lat.is_owned(i, j, k)) acc[13] = 1;
+    return;
+  }
+  stencil27_assemble_cell<T, 0, 0, 0>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 0, 0, 1>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 0, 1, 0>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 0, 1, 1>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 1, 0, 0>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 1, 0, 1>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 1, 1, 0>(lat, tb, xv, kappa, kc, i, j, k, acc);
+  stencil27_assemble_cell<T, 1, 1, 1>(lat, tb, xv, kappa, kc, i, j, k, acc);
+#pragma unroll
+  for (int di = -1; di <= 1; ++di)
+#pragma unroll
+    for (int dj = -1; dj <= 1; ++dj)
+#pragma unroll
+      for (int dk = -1; dk <= 1; ++dk) {
+        const bool in = i + di >= 0 && i + di < lat.L[0] && j + dj >= 0 && j + dj < lat.L[1] &&
+                        k + dk >= 0 && k + dk < lat.L[2];
+        if (!in || lat.is_bc(i + di, j + dj, k + dk)) acc[(di + 1) * 9 + (dj + 1) * 3 + (dk + 1)] = 0;
+      }
 }
 
 // Entry `at` of one Chebyshev-Jacobi step, y = A z computed by the caller:

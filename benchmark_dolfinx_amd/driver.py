@@ -135,7 +135,8 @@ def laplace_action(pb: PoissonProblem, nreps: int, use_cg: bool, mat_comp: bool,
     precond="pmg" (CG only): a p-multigrid V-cycle (solvers/pmg.py; `pmg_opts`:
     keyword arguments of `PMultigrid`, `tail_nodes` among them: its one-launch
     tail, whose "tail_nodes" / "tail_levels" then appear in the JSON's "pmg"
-    block, and `q1_operator`: the degree-1 levels on assembled stencils); the
+    block, `q1_operator`: the degree-1 levels on assembled stencils, and
+    `q1_assembly`: those stencils built on the device); the
     CSR comparison solve is
     preconditioned with the same `PMultigrid` object, so the error norm
     again compares two solves with one algorithm."""

@@ -319,6 +319,36 @@ class PoissonProblem:
             self._dinv = torch.reciprocal(self.operator_diagonal())
         return self._dinv
 
+    # ----------------------------------------------------------- stencil
+    def stencil27(self, assembly: str = "csr") -> torch.Tensor:
+        """The assembled operator of this degree-1 problem as a 27-point
+        stencil (`ops.kernels.stencil27`): shape (27, nstore), the problem's
+        dtype, on its device; a ghost-plane row holds this rank's partial sums.
+
+        assembly: "csr" = the host's `CSROperator`, sorted into the 27 planes
+        and uploaded; "direct" = written in the storage layout by
+        `stencil27_assemble` (lap_stencil27_assemble.h on the GPU, its host twin
+        on the CPU) from the vertices, kappa and the tables, with no matrix and
+        no host work.  The two agree to rounding, and exactly in every entry
+        that is 0 or 1 by definition (Dirichlet rows and columns, neighbours
+        outside the lattice, the storage padding)."""
+        if not isinstance(assembly, str) or assembly not in ("csr", "direct"):
+            raise ValueError(f"assembly must be 'csr' or 'direct', got {assembly!r}")
+        if self.degree != 1:
+            raise ValueError("stencil27 needs a degree-1 problem")
+        if assembly == "csr":
+            from ..ops.kernels import stencil27
+            return torch.from_numpy(stencil27(CSROperator(self), self.lat)).to(self.device)
+        with timed("~setup stencil27"):
+            S = torch.empty((27, self.lat.nstore), dtype=self.dtype, device=self.device)
+            if self.platform == "gpu":
+                self.kernels.stencil27_assemble(self.xv, self.kappa, self.kc, S)
+            else:
+                from ..ops.kernels import HostKernels
+                HostKernels(self.lat, self.dtype, self.tables).stencil27_assemble(
+                    self.xv, self.kappa, self.kc, S)
+        return S
+
     @property
     def ndofs_global(self) -> int:
         return self.lat.ndofs_global

@@ -144,6 +144,7 @@ def declare(lib) -> None:
         _d(lib, f"bdx_restrict_row_{suf}", [vp, vp, vp, vp, vp, vp, vp])
         _d(lib, f"bdx_stencil27_apply_{suf}", [vp, vp, vp, vp, vp])
         _d(lib, f"bdx_stencil27_cheb_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp, f64, f64, vp])
+        _d(lib, f"bdx_stencil27_assemble_{suf}", [vp, i32, vp, vp, vp, vp, vp, f64, vp, vp, vp])
         _d(lib, f"bdx_pmg_tail_{suf}", [vp, vp, i32, i64, vp, vp, vp])
         _d(lib, f"bdx_box_copy_{suf}", [i32, vp, i64, i64, vp, i32, i64, vp, vp])
         _d(lib, f"bdx_box_copy_lat_{suf}", [i32, vp, vp, vp, i32, i64, vp, vp])

@@ -50,6 +50,7 @@ def declare(lib) -> None:
         _d(lib, f"bdx_cpu_pmg_tail_{suf}", [vp, i32, i64, vp, vp], i32)
         _d(lib, f"bdx_cpu_stencil27_{suf}", [vp, vp, vp, vp])
         _d(lib, f"bdx_cpu_stencil27_cheb_{suf}", [vp, vp, vp, vp, vp, vp, vp, vp, f64, f64], i32)
+        _d(lib, f"bdx_cpu_stencil27_assemble_{suf}", [vp, i32, vp, vp, vp, vp, vp, f64, vp, vp], i32)
     # the precision boundary of the mixed multigrid solve
     _d(lib, "bdx_cpu_demote_f64_f32", [i64, i64, i64, i64, i64, vp, vp])
     _d(lib, "bdx_cpu_promote_f32_f64", [i64, i64, i64, i64, i64, vp, vp])

@@ -119,6 +119,20 @@ def _stencil27_check(lat, dtype, S, *vecs) -> None:
                             f"got {v.dtype} {tuple(v.shape)}")
 
 
+def _stencil27_assemble_check(lat, dtype, xv, kc, S) -> None:
+    """S as `_stencil27_check`; xv the lattice's vertices (n + 1 per axis, x 3)
+    and kc its per-cell kappa or None, contiguous and of `dtype` (the assembly
+    indexes them by cell)."""
+    _stencil27_check(lat, dtype, S)
+    n = tuple(int(m) for m in lat.n)
+    for name, v, shape in (("xv", xv, tuple(m + 1 for m in n) + (3,)), ("kc", kc, n)):
+        if v is None and name == "kc":
+            continue
+        if v is None or v.dtype != dtype or tuple(v.shape) != shape or not v.is_contiguous():
+            raise TypeError(f"stencil27_assemble: expected contiguous {dtype} {name} of shape "
+                            f"{shape}")
+
+
 class PmgTail:
     """The device data of the V-cycle tail (csrc/hip/pmg_tail.h): per level of
     `levels` (consecutive degree-1 levels of a `PMultigrid`, the last one its
@@ -127,13 +141,13 @@ class PmgTail:
     pointers of its stencil, `dinv`, `bc`, work vectors and transfer tables,
     and its Chebyshev coefficients, kept on the host (`host`, read by the
     launch checks) and on the device (`dev`, read by the kernel).  Everything
-    is uploaded here, once; the tensors the table points to are kept alive."""
+    is uploaded here, once; the tensors the table points to are kept alive.
+    `assembly`: how the stencils are built (`PoissonProblem.stencil27`)."""
 
     WORDS = hip_api.CONSTANTS["kTailWords"]
     MAX_NODES = hip_api.CONSTANTS["kTailMaxNodes"]
 
-    def __init__(self, levels, dtype, device):
-        from ..models.poisson import CSROperator  # models.poisson imports this module
+    def __init__(self, levels, dtype, device, assembly: str = "csr"):
         self.nlev = len(levels)
         self.dtype = dtype
         self.shape = tuple(levels[0].pb.lat.shape)
@@ -144,7 +158,7 @@ class PmgTail:
         self.S, self._keep = [], []
         off = self.nlev * W
         for l, lv in enumerate(levels):
-            S = torch.from_numpy(stencil27(CSROperator(lv.pb), lv.pb.lat)).to(device)
+            S = lv.pb.stencil27(assembly)
             self.S.append(S)
             w = words[l]
             w.lat = hip_api.Lattice.from_buffer_copy(lv.latd)
@@ -379,6 +393,17 @@ class HipKernels:
                                              ptr(r), ptr(z_in), ptr(d), ptr(z_out), float(a),
                                              float(b), _stream()), "stencil27_cheb")
 
+    def stencil27_assemble(self, xv, kappa: float, kc, S):
+        """S = the assembled 27-point stencil of this (degree-1) lattice, every
+        entry written (lap_stencil27_assemble.h): `stencil27` of the assembled
+        matrix, built on the device from the vertices xv and kappa (kc: per
+        cell, or None)."""
+        _stencil27_assemble_check(self.lat, self.dtype, xv, kc, S)
+        t = self.t
+        _check(self._f("bdx_stencil27_assemble")(ptr(self.latd), t.nq, ptr(t.phi0), ptr(t.dphi1),
+                                                 ptr(t.wts), ptr(t.qpts), ptr(xv), float(kappa),
+                                                 ptr(kc), ptr(S), _stream()), "stencil27_assemble")
+
     def pmg_tail(self, tail: PmgTail, r, z):
         """z = the V-cycle of the tail's levels applied to r, in one launch of
         one workgroup (pmg_tail.h); r, z: vectors of its first level."""
@@ -439,10 +464,11 @@ class HostKernels:
     """The p-multigrid kernels of `HipKernels` on the host twins
     (csrc/host/bdx_host_mg.cpp), so the CPU platform runs the same Python path."""
 
-    def __init__(self, lat, dtype):
+    def __init__(self, lat, dtype, tables=None):
         self.lib = native.host()
         self.lat = lat
         self.latd = lat.as_int64()
+        self.t = None if tables is None else TableSet(tables)  # stencil27_assemble only
         self.dtype = dtype
         self.suf = _suf(dtype)
         self.o = lat.owned_hi
@@ -508,6 +534,18 @@ class HostKernels:
                                              ptr(r), ptr(z_in), ptr(d), ptr(z_out), float(a),
                                              float(b)):
             raise ValueError("stencil27_cheb: not a degree-1 lattice, or z_out is z_in")
+
+    def stencil27_assemble(self, xv, kappa: float, kc, S):
+        """`HipKernels.stencil27_assemble` on the host twin."""
+        _stencil27_assemble_check(self.lat, self.dtype, xv, kc, S)
+        t = self.t
+        if t is None:
+            raise ValueError("stencil27_assemble: these HostKernels were built without tables")
+        if self._f("bdx_cpu_stencil27_assemble")(ptr(self.latd), t.nq, ptr(t.phi0), ptr(t.dphi1),
+                                                 ptr(t.wts), ptr(t.qpts), ptr(xv), float(kappa),
+                                                 ptr(kc), ptr(S)):
+            raise ValueError("stencil27_assemble: not a degree-1 lattice with 2 or 3 quadrature "
+                             "points per axis")
 
     def _rows(self, a, da, out, do):
         for v, dt in ((a, da), (out, do)):

@@ -78,6 +78,13 @@ an odd number of steps from a nonzero guess ends with a copy.  On more ranks S
 holds the rank's own cells, a ghost row its partial sums, so a step keeps
 `CSROperator.apply`'s protocol: forward exchange, `stencil27_apply` on every
 local row, reverse exchange, `cheb_step`.
+
+Stencil assembly (`q1_assembly="direct"`, default "csr"): the stencils of the
+stencil levels and of the tail are written by `PoissonProblem.stencil27
+("direct")` (csrc/hip/lap_stencil27_assemble.h, one launch per level; host twin
+in csrc/host/bdx_host_mg.cpp) in place of `CSROperator` on the host, the sort
+into planes and the upload.  The entries agree with the host's to rounding; the
+rest of setup is untouched.
 """
 
 from __future__ import annotations
@@ -165,14 +172,22 @@ class PMultigrid:
 
     q1_operator: "matfree" = every level applies its matrix-free operator;
     "stencil" = the degree-1 levels outside the tail apply their assembled
-    27-point stencil `lv.S` (module docstring)."""
+    27-point stencil `lv.S` (module docstring).
+
+    q1_assembly: how those stencils and the tail's are built
+    (`PoissonProblem.stencil27`): "csr" = from the host's assembled matrix;
+    "direct" = by the assembly kernel on the problem's device, so that setup
+    builds no `CSROperator`; refused where there is nothing to assemble
+    (q1_operator="matfree" without a tail).  Setup is otherwise the same:
+    lambda_max, `dinv` and every coefficient do not depend on it."""
 
     TAIL_MAX_NODES = CONSTANTS["kTailMaxNodes"]
 
     def __init__(self, pb: PoissonProblem, smooth_degree: int = 2, smooth_range: float = 10.0,
                  coarse_degree: int = 8, coarse_range: float = 100.0, eig_iters: int = 10,
                  h_levels: int = 0, cycle_dtype: torch.dtype | None = None, tail_nodes: int = 0,
-                 p_transfer: str = "cell", q1_operator: str = "matfree"):
+                 p_transfer: str = "cell", q1_operator: str = "matfree",
+                 q1_assembly: str = "csr"):
         if smooth_degree < 1 or coarse_degree < 1 or eig_iters < 1:
             raise ValueError("smoother degrees and eig_iters must be positive")
         if smooth_range <= 1.0 or coarse_range <= 1.0:
@@ -192,6 +207,12 @@ class PMultigrid:
         if q1_operator not in ("matfree", "stencil"):
             raise ValueError(f"q1_operator must be 'matfree' or 'stencil', got {q1_operator!r}")
         self.q1_operator = q1_operator
+        if not isinstance(q1_assembly, str) or q1_assembly not in ("csr", "direct"):
+            raise ValueError(f"q1_assembly must be 'csr' or 'direct', got {q1_assembly!r}")
+        if q1_assembly == "direct" and q1_operator == "matfree" and tail_nodes == 0:
+            raise ValueError("q1_assembly='direct' has nothing to assemble: it needs "
+                             "q1_operator='stencil' or tail_nodes > 0")
+        self.q1_assembly = q1_assembly
         if cycle_dtype is None:
             cycle_dtype = pb.dtype
         if cycle_dtype not in (torch.float32, torch.float64) or \
@@ -257,15 +278,13 @@ class PMultigrid:
             if start < len(self.levels):
                 from ..ops.kernels import PmgTail
                 self.tail_start, self.tail_levels = start, len(self.levels) - start
-                self.tail = PmgTail(self.levels[start:], cycle_dtype, pb.device)
+                self.tail = PmgTail(self.levels[start:], cycle_dtype, pb.device, q1_assembly)
         # the stencils of the degree-1 levels above the tail
         if self.q1_operator == "stencil":
-            from ..models.poisson import CSROperator
-            from ..ops.kernels import stencil27
             end = len(self.levels) if self.tail_start is None else self.tail_start
             for lv in self.levels[:end]:
                 if lv.pb.degree == 1:
-                    lv.S = torch.from_numpy(stencil27(CSROperator(lv.pb), lv.pb.lat)).to(pb.device)
+                    lv.S = lv.pb.stencil27(q1_assembly)
 
     # ---------------------------------------------------------------- setup
     @staticmethod
@@ -433,6 +452,8 @@ class PMultigrid:
             out["p_transfer"] = self.p_transfer
         if self.q1_operator != "matfree":
             out["q1_operator"] = self.q1_operator
+        if self.q1_assembly != "csr":
+            out["q1_assembly"] = self.q1_assembly
         return out
 
     def close(self) -> None:

@@ -15,6 +15,9 @@ fused CG on one GPU: one JSON line per configuration (profiles/pmg.md).
                                                              (their kernels against the launches they replace)
   python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --q1 matfree,stencil --no-yardsticks
                                                              (stencil levels, profiles/pmg_q1stencil.md)
+  python scripts/pmg_compare.py --hlevels -1 --cycle_float 32 --q1 matfree,stencil \
+                                --q1-assembly csr,direct --no-yardsticks
+                                                             (their assembly, profiles/pmg_q1assemble.md)
 
 One process per configuration.  FP64, qmode 1 (GLL).  Three variants, each on
 its own auto-selected operator:
@@ -47,6 +50,16 @@ its own auto-selected operator:
              `stencil27_apply` and `stencil27_cheb` against the matrix-free apply and apply +
              `cheb_step` they replace, with the effective TB/s over S and the vectors (apply:
              27 + 2 values per node, fused step: 27 + 6)
+
+  <v>_s27d   (--q1-assembly csr,direct, with --q1 matfree,stencil) every v_s27 again with
+             PMultigrid(q1_assembly="direct"): the stencils written by the assembly kernel
+             (csrc/hip/lap_stencil27_assemble.h) instead of the host's CSR matrix; interleaved like
+             hpmg, the yardstick of v_s27d is v_s27.  The "q1_assembly" block holds, per pair, the
+             iterations and ms per iteration of both, the wall time to build the matfree, the csr
+             and the direct hierarchy (--reps repetitions, the three in turn in this process) and,
+             per stencil level, the assembly kernel alone: ms, the flop rate for a source-level
+             count of 337 flops per quadrature point of each of a node's 8 cells (an FMA = 2), and
+             the ratio to the time of storing S at the measured stream rate
 
 --transfer-kernels: no solve.  For every p-pair of the configured problem, in FP64 and FP32
 vectors, device-event times (the median of --reps batches of five calls, the candidates
@@ -188,6 +201,9 @@ def main(argv=None) -> int:
     ap.add_argument("--q1", default="matfree",
                     help="comma-separated q1_operator values (matfree,stencil): stencil adds "
                          "<variant>_s27")
+    ap.add_argument("--q1-assembly", default="csr",
+                    help="comma-separated q1_assembly values (csr,direct): direct adds "
+                         "<variant>_s27d (needs --q1 matfree,stencil)")
     ap.add_argument("--transfer-kernels", action="store_true",
                     help="time the row transfer kernels against the launches they replace, and stop")
     ap.add_argument("--no-yardsticks", action="store_true",
@@ -215,6 +231,11 @@ def main(argv=None) -> int:
     q1s = [t for t in a.q1.split(",") if t]
     if not q1s or set(q1s) - {"matfree", "stencil"} or "matfree" not in q1s:
         raise SystemExit("--q1 takes matfree or matfree,stencil (matfree is the yardstick)")
+    asms = [t for t in a.q1_assembly.split(",") if t]
+    if not asms or set(asms) - {"csr", "direct"} or "csr" not in asms:
+        raise SystemExit("--q1-assembly takes csr or csr,direct (csr is the yardstick)")
+    if "direct" in asms and "stencil" not in q1s:
+        raise SystemExit("--q1-assembly csr,direct needs --q1 matfree,stencil")
     nx = compute_mesh_size(a.ndofs, a.degree)
     if a.transfer_kernels:
         print(json.dumps(transfer_kernels(a, nx)), flush=True)
@@ -223,8 +244,10 @@ def main(argv=None) -> int:
     b = pb.assemble_rhs()
 
     def pmg_kwargs(variant):
-        """The PMultigrid options a variant's name spells: [h]pmg[32][_tN][_row][_s27]."""
+        """The PMultigrid options a variant's name spells: [h]pmg[32][_tN][_row][_s27[d]]."""
         kw = {}
+        if variant.endswith("_s27d"):
+            kw["q1_assembly"], variant = "direct", variant[:-1]
         if variant.endswith("_s27"):
             kw["q1_operator"], variant = "stencil", variant[:-4]
         if variant.endswith("_row"):
@@ -266,6 +289,8 @@ def main(argv=None) -> int:
         variants += tuple(f"{v}_row" for v in variants if "pmg" in v)
     if "stencil" in q1s:
         variants += tuple(f"{v}_s27" for v in variants if "pmg" in v)
+    if "direct" in asms:
+        variants += tuple(f"{v}d" for v in variants if v.endswith("_s27"))
     solves = tuple(v for v in variants if "pmg" in v)
     state = {v: make(v) for v in variants}
     pmg = state["pmg"][1].pmg
@@ -471,12 +496,50 @@ def main(argv=None) -> int:
                     "tb_per_s": {"stencil27_apply": 29 * n * size / (t["stencil27_apply"] * 1e-3) / 1e12,
                                  "stencil27_cheb": 33 * n * size / (t["stencil27_cheb"] * 1e-3) / 1e12}})
             rec["q1"][v] = blk
+    if "direct" in asms:
+        rec["q1_assembly"] = {}
+        for v in variants:
+            if not v.endswith("_s27d"):
+                continue
+            dp, y = state[v][1].pmg, v[:-1]
+            kws = {"matfree": pmg_kwargs(y[:-4]), "csr": pmg_kwargs(y), "direct": pmg_kwargs(v)}
+            built = {k: [] for k in kws}
+            for _ in range(a.reps):
+                for k, kw in kws.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    h = PMultigrid(pb, **kw)
+                    torch.cuda.synchronize()
+                    built[k].append(time.perf_counter() - t0)
+                    h.close()
+                    del h
+            blk = {"info": dp.info(), "yardstick": y,
+                   "iters_to_tol": {y: iters.get(y), v: iters.get(v)},
+                   "ms_per_iter": {y: ms[y], v: ms[v]},
+                   "build_s": {k: spread(t) for k, t in built.items()},
+                   "build_s_all": built,
+                   "direct_faster_every_rep": all(d < c for d, c in zip(built["direct"],
+                                                                        built["csr"])),
+                   "levels": []}
+            for dl in dp.levels:
+                if dl.S is None:
+                    continue
+                lpb, size = dl.pb, dl.S.element_size()
+                nodes = int(lpb.lat.L[0] * lpb.lat.L[1] * lpb.lat.L[2])
+                t = timed(lambda: lpb.kernels.stencil27_assemble(lpb.xv, lpb.kappa, lpb.kc, dl.S))
+                flops = 8 * lpb.tables.nq ** 3 * 337 * nodes
+                store_ms = 27 * dl.S.shape[1] * size / (stream_tbs * 1e12) * 1e3
+                blk["levels"].append({"nodes": nodes, "float": 8 * size, "nq": lpb.tables.nq,
+                                      "assemble_ms": t, "model_tflops": flops / (t * 1e-3) / 1e12,
+                                      "store_ms_at_stream_rate": store_ms,
+                                      "ratio_to_store": t / store_ms})
+            rec["q1_assembly"][v] = blk
     if tails:
         # per tailed variant: the whole cycle, and the tail's one call against the
         # untailed hierarchy's `_vcycle` from the same level (the launches it replaces)
         rec["tail"] = {}
         for v in variants:
-            if "_t" not in v or v.endswith("_row") or v.endswith("_s27"):
+            if "_t" not in v or v.endswith(("_row", "_s27", "_s27d")):
                 continue
             tp = state[v][1].pmg
             up = state[v.partition("_t")[0]][1].pmg
@@ -542,7 +605,7 @@ def main(argv=None) -> int:
         rec["hpmg_parts_ms"] = hparts
         hp.close()
     for v in variants:
-        if v.endswith("_row") or v.endswith("_s27"):
+        if v.endswith(("_row", "_s27", "_s27d")):
             state[v][1].pmg.close()
     pmg.close()
     for op, _, _ in state.values():
