@@ -25,8 +25,7 @@ import torch
 from ..fem.mesh import (LocalLattice, cell_coefficients, make_local_lattice,
                         vertex_coordinates)
 from ..fem.quadrature import OperatorTables
-from ..ops import native
-from ..ops.native import ptr
+from ..ops.kernels import HipKernels, HostKernels
 from ..parallel.comm import Comm
 from ..parallel.halo import HaloExchange
 from ..utils.timing import timed
@@ -131,14 +130,10 @@ class PoissonProblem:
             xv = xv.astype(npdt)
             self.xv_host = np.ascontiguousarray(xv)
             self.xv = torch.from_numpy(self.xv_host).to(self.device)
-        self.host_tables = {k: np.ascontiguousarray(v, dtype=npdt) for k, v in dict(
-            phi0=self.tables.phi0, dphi1=self.tables.dphi1, wts=self.tables.qwts,
-            qpts=self.tables.qpts, nodes=self.tables.nodes, B=self.tables.B,
-            Dd=self.tables.Dd).items()}
-        self.kernels = None
-        if platform == "gpu":
-            from ..ops.kernels import HipKernels
-            self.kernels = HipKernels(self.lat, self.tables, dtype)
+        # the platform's kernel front-end, chosen here and nowhere else
+        self._host_kernels = None
+        self.kernels = HipKernels(self.lat, self.tables, dtype) if platform == "gpu" \
+            else self.host_kernels
         self.halo = HaloExchange(self.lat, comm, dtype, self.device, self.kernels)
         # kept alive for ctypes calls (never pass temporaries to ptr())
         self.latd = self.lat.as_int64()
@@ -180,6 +175,15 @@ class PoissonProblem:
         return cls(parent.comm, lat.ncells_global, 1, parent.qmode, parent.use_gauss, parent.dtype,
                    parent.platform, parent.perturb, parent.coefficient, shear=parent.shear,
                    partition=parent.partition, lat=lat, xv=xv, kc=kc)
+
+    @property
+    def host_kernels(self) -> HostKernels:
+        """The host library's front-end: `kernels` itself on the CPU platform,
+        on the GPU built on first use for the host-only setup work
+        (`interpolate_f`, `CSROperator`'s assembly)."""
+        if self._host_kernels is None:
+            self._host_kernels = HostKernels(self.lat, self.dtype, self.tables)
+        return self._host_kernels
 
     # --------------------------------------------------------------- vectors
     @property
@@ -250,9 +254,7 @@ class PoissonProblem:
     def interpolate_f(self) -> torch.Tensor:
         """f at the physical dof nodes (src/main.cpp:81-92), all local points."""
         f = np.zeros(self.lat.shape, dtype=_np_dtype(self.dtype))
-        lib = native.host()
-        getattr(lib, f"bdx_cpu_interp_f_{self.suf}")(
-            ptr(self.latd), ptr(self.host_tables["nodes"]), ptr(self.xv_host), ptr(f))
+        self.host_kernels.interp_f(self.xv_host, f)
         return torch.from_numpy(f).to(self.device)
 
     def assemble_rhs(self) -> torch.Tensor:
@@ -262,14 +264,7 @@ class PoissonProblem:
             b = self.new_vector()
             lo = np.zeros(3, dtype=np.int64)
             hi = np.array(self.lat.n, dtype=np.int64)
-            if self.platform == "gpu":
-                self.kernels.v1_apply(2, None, self.xv, 0.0, f, b, lo, hi)
-            else:
-                t = self.host_tables
-                getattr(native.host(), f"bdx_cpu_mass_{self.suf}")(
-                    ptr(self.latd), self.tables.nq, ptr(t["phi0"]), ptr(t["dphi1"]),
-                    ptr(t["wts"]), ptr(t["qpts"]), ptr(t["nodes"]), int(self.tables.is_identity),
-                    ptr(self.xv_host), ptr(f.numpy()), ptr(b.numpy()), ptr(lo), ptr(hi))
+            self.kernels.v1_apply(2, None, self.xv, 0.0, f, b, lo, hi)
             self.halo.reverse(b)
             b.masked_fill_(self.bc_mask(), 0.0)
             self.halo.forward(b)
@@ -299,14 +294,7 @@ class PoissonProblem:
                 d[:, :, : self.lat.L[2]] = 0
                 lo = np.zeros(3, dtype=np.int64)
                 hi = np.array(self.lat.n, dtype=np.int64)
-                if self.platform == "gpu":
-                    self.kernels.diagonal(self.xv, self.kappa, self.kc, d, lo, hi)
-                else:
-                    t = self.host_tables
-                    getattr(native.host(), f"bdx_cpu_diag_{self.suf}")(
-                        ptr(self.latd), self.tables.nq, ptr(t["B"]), ptr(t["Dd"]), ptr(t["wts"]),
-                        ptr(t["qpts"]), ptr(self.xv_host), self.kappa, ptr(self.kc_host),
-                        ptr(d.numpy()), ptr(lo), ptr(hi))
+                self.kernels.diagonal(self.xv, self.kappa, self.kc, d, lo, hi)
                 self.halo.reverse(d)
                 d.masked_fill_(self.bc_mask(), 1.0)
                 self.halo.forward(d)
@@ -341,12 +329,7 @@ class PoissonProblem:
             return torch.from_numpy(stencil27(CSROperator(self), self.lat)).to(self.device)
         with timed("~setup stencil27"):
             S = torch.empty((27, self.lat.nstore), dtype=self.dtype, device=self.device)
-            if self.platform == "gpu":
-                self.kernels.stencil27_assemble(self.xv, self.kappa, self.kc, S)
-            else:
-                from ..ops.kernels import HostKernels
-                HostKernels(self.lat, self.dtype, self.tables).stencil27_assemble(
-                    self.xv, self.kappa, self.kc, S)
+            self.kernels.stencil27_assemble(self.xv, self.kappa, self.kc, S)
         return S
 
     @property
@@ -358,57 +341,50 @@ class PoissonProblem:
         return self.lat.ncells_global_total
 
 
-class MatFreeLaplacianCPU:
+class _MatFreeLaplacian:
+    """y = A u through the problem's kernel front-end: the interior cells
+    while the forward exchange of u is in flight, the boundary cells after it,
+    then the reverse exchange of y.  `G`: the stored geometry factors
+    (reference layout [c][6][nq^3], src/laplacian.hpp:515-541), or None to
+    compute them per point from the cell's vertices."""
+
+    def _cells(self, u, y, lo, hi):
+        pb = self.pb
+        pb.kernels.v1_apply(0 if self.G is not None else 1, self.G, pb.xv, pb.kappa, u, y, lo, hi,
+                            pb.kc)
+
+    def apply(self, u: torch.Tensor, y: torch.Tensor) -> None:
+        pb, lat = self.pb, self.pb.lat
+        y.zero_()
+        work = pb.halo.forward_begin(u)
+        self._cells(u, y, *lat.interior_cell_box())
+        pb.halo.forward_end(u, work)
+        for lo, hi in lat.boundary_cell_boxes():
+            self._cells(u, y, lo, hi)
+        pb.halo.reverse(y)
+
+
+class MatFreeLaplacianCPU(_MatFreeLaplacian):
     """CPU operator (C++/OpenMP, both qmodes; src/laplacian.hpp:450-771)."""
 
-    # geometry factors precomputed per cell (reference layout [c][6][nq^3],
-    # src/laplacian.hpp:515-541) when they fit in this many bytes, else
-    # computed per point on the fly.  Default 0 (on the fly): on this 8-core
+    # geometry factors precomputed per cell when they fit in this many bytes,
+    # else computed per point on the fly.  Default 0 (on the fly): on this 8-core
     # host the stored-G apply is memory-bound and slower at 8 threads (73 vs
     # 49 ms per 1 M DoF Q3 apply; faster on one thread, 182 vs 365 ms).
     # BDX_CPU_G_MAX_BYTES overrides.
     G_MAX_BYTES = 0
 
     def __init__(self, problem: PoissonProblem):
-        import os
         self.pb = problem
-        self.lib = native.host()
-        self._fn = getattr(self.lib, f"bdx_cpu_stiffness_g_{problem.suf}")
-        self.latd = problem.lat.as_int64()
-        nq = problem.tables.nq
-        ncells = int(np.prod(problem.lat.n))
-        nbytes = ncells * 6 * nq ** 3 * problem.new_vector().element_size()
+        n = int(np.prod(problem.lat.n)) * 6 * problem.tables.nq ** 3
         self.G = None
-        if nbytes <= int(os.environ.get("BDX_CPU_G_MAX_BYTES", self.G_MAX_BYTES)):
-            t = problem.host_tables
-            self.G = np.empty(ncells * 6 * nq ** 3, dtype=t["wts"].dtype)
-            getattr(self.lib, f"bdx_cpu_geometry_{problem.suf}")(
-                ptr(self.latd), nq, ptr(t["wts"]), ptr(t["qpts"]), ptr(problem.xv_host),
-                ptr(self.G))
-
-    def _cells(self, u, y, lo, hi):
-        t = self.pb.host_tables
-        lo = np.asarray(lo, dtype=np.int64)
-        hi = np.asarray(hi, dtype=np.int64)
-        self._fn(ptr(self.latd), self.pb.tables.nq, ptr(t["phi0"]), ptr(t["dphi1"]),
-                 ptr(t["wts"]), ptr(t["qpts"]), ptr(t["nodes"]),
-                 int(self.pb.tables.is_identity), ptr(self.pb.xv_host),
-                 ptr(self.G) if self.G is not None else None, self.pb.kappa,
-                 ptr(self.pb.kc_host), ptr(u.numpy()), ptr(y.numpy()), ptr(lo), ptr(hi))
-
-    def apply(self, u: torch.Tensor, y: torch.Tensor) -> None:
-        lat = self.pb.lat
-        y.zero_()
-        work = self.pb.halo.forward_begin(u)
-        lo, hi = lat.interior_cell_box()
-        self._cells(u, y, lo, hi)
-        self.pb.halo.forward_end(u, work)
-        for lo, hi in lat.boundary_cell_boxes():
-            self._cells(u, y, lo, hi)
-        self.pb.halo.reverse(y)
+        if n * problem.new_vector().element_size() <= int(
+                os.environ.get("BDX_CPU_G_MAX_BYTES", self.G_MAX_BYTES)):
+            self.G = np.empty(n, dtype=_np_dtype(problem.dtype))
+            problem.kernels.geometry(problem.xv, self.G)
 
 
-class MatFreeLaplacianGPU:
+class MatFreeLaplacianGPU(_MatFreeLaplacian):
     """Matrix-free operator on the GPU.
 
     geometry="stored": G precomputed once (6 nq^3 values per cell, the
@@ -418,30 +394,16 @@ class MatFreeLaplacianGPU:
 
     def __init__(self, problem: PoissonProblem, geometry: str = "stored"):
         self.pb = problem
-        self.k = problem.kernels
         self.geometry = geometry
         self.G = None
         if geometry == "stored":
-            lat = problem.lat
             nq3 = problem.tables.nq ** 3
             with timed("~setup geometry"):
-                self.G = torch.empty(lat.ncells_local * 6 * nq3, dtype=problem.dtype,
+                self.G = torch.empty(problem.lat.ncells_local * 6 * nq3, dtype=problem.dtype,
                                      device=problem.device)
-                self.k.geometry(problem.xv, self.G)
+                problem.kernels.geometry(problem.xv, self.G)
         elif geometry != "otf":
             raise ValueError(f"unknown geometry mode {geometry}")
-        self.mode = 0 if geometry == "stored" else 1
-
-    def apply(self, u: torch.Tensor, y: torch.Tensor) -> None:
-        pb, lat = self.pb, self.pb.lat
-        y.zero_()
-        work = pb.halo.forward_begin(u)
-        lo, hi = lat.interior_cell_box()
-        self.k.v1_apply(self.mode, self.G, pb.xv, pb.kappa, u, y, lo, hi, pb.kc)
-        pb.halo.forward_end(u, work)
-        for lo, hi in lat.boundary_cell_boxes():
-            self.k.v1_apply(self.mode, self.G, pb.xv, pb.kappa, u, y, lo, hi, pb.kc)
-        pb.halo.reverse(y)
 
 
 class CSROperator:
@@ -458,24 +420,17 @@ class CSROperator:
         lat = problem.lat
         if lat.nstore >= 2 ** 31:
             raise RuntimeError("Too many matrix rows for int32 columns")
-        lib = native.host()
-        fn = getattr(lib, f"bdx_cpu_csr_{problem.suf}")
-        t = problem.host_tables
-        npdt = _np_dtype(problem.dtype)
+        args = (problem.xv_host, problem.kappa, problem.kc_host)
         row_ptr = np.zeros(lat.nstore + 1, dtype=np.int64)
-        self.latd = problem.latd
-        args = (ptr(self.latd), problem.tables.nq, ptr(t["B"]), ptr(t["Dd"]),
-                ptr(t["wts"]), ptr(t["qpts"]), ptr(problem.xv_host), problem.kappa,
-                ptr(problem.kc_host))
         with timed("% Create CPU MatrixCSR"):
-            nnz = fn(*args, ptr(row_ptr), 0, 0, 1)
+            nnz = problem.host_kernels.csr(*args, row_ptr)
             if nnz >= 2 ** 31:
                 raise RuntimeError("Too many matrix entries, need 64-bit row_ptr.")
             cols = np.zeros(nnz, dtype=np.int32)
-            vals = np.zeros(nnz, dtype=npdt)
+            vals = np.zeros(nnz, dtype=_np_dtype(problem.dtype))
             row_ptr[:] = 0
         with timed("% Assemble CPU MatrixCSR"):
-            fn(*args, ptr(row_ptr), ptr(cols), ptr(vals), 0)
+            problem.host_kernels.csr(*args, row_ptr, cols, vals)
         self.nnz = int(nnz)
         self.nrows = lat.nstore
         # Column split of every row, as DOLFINx's MatrixCSR off-diagonal block
@@ -524,13 +479,7 @@ class CSROperator:
         return d
 
     def _spmv(self, beg, end, x, y, acc):
-        pb = self.pb
-        if pb.platform == "gpu":
-            pb.kernels.spmv(self.nrows, beg, end, self.cols, self.vals, x, y, acc)
-        else:
-            getattr(native.host(), f"bdx_cpu_spmv_{pb.suf}")(
-                self.nrows, ptr(beg.numpy()), ptr(end.numpy()), ptr(self.cols.numpy()),
-                ptr(self.vals.numpy()), ptr(x.numpy()), ptr(y.numpy()), int(acc))
+        self.pb.kernels.spmv(self.nrows, beg, end, self.cols, self.vals, x, y, acc)
 
     def apply(self, x: torch.Tensor, y: torch.Tensor) -> None:
         """y = A x: owned-column pass while the forward exchange is in

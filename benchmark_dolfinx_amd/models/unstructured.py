@@ -296,17 +296,14 @@ class DofmapLaplacianCPU:
     name = "dofmap"
 
     def __init__(self, problem, geometry: str = "stored", mesh: UnstructuredMesh | None = None):
-        from ..ops import native
         if problem.platform != "cpu":
             raise ValueError("DofmapLaplacianCPU runs on the CPU platform")
         if geometry not in ("otf", "stored"):
             raise ValueError(f"unknown geometry mode {geometry}")
         self.pb = problem
         self.geometry = f"dofmap-{geometry}"
-        self.lib = native.host()
-        suf = problem.suf
-        self._fn = getattr(self.lib, f"bdx_cpu_dofmap_{suf}")
-        npdt = np.float64 if suf == "f64" else np.float32
+        self.k = problem.kernels
+        npdt = np.float64 if problem.dtype == torch.float64 else np.float32
         with timed("~setup dofmap"):
             self.mesh = m = mesh or UnstructuredMesh.from_problem(problem)
             self.cdofs = np.ascontiguousarray(m.cell_dofs, dtype=np.int32)
@@ -316,26 +313,15 @@ class DofmapLaplacianCPU:
             self.inner = np.ascontiguousarray(m.interior_cells, dtype=np.int32)
             self.outer = np.ascontiguousarray(m.boundary_cells, dtype=np.int32)
             self.kc = None if m.kc is None else np.ascontiguousarray(m.kc, dtype=npdt)
-            t = problem.host_tables
-            self.t = t
             self.G = None
             if geometry == "stored":
-                nq = problem.tables.nq
-                self.G = np.empty(m.ncells * 6 * nq ** 3, dtype=npdt)
-                getattr(self.lib, f"bdx_cpu_dofmap_geometry_{suf}")(
-                    problem.lat.degree, nq, native.ptr(t["wts"]), native.ptr(t["qpts"]),
-                    m.ncells, native.ptr(self.cverts), native.ptr(self.coords),
-                    native.ptr(self.G))
+                self.G = np.empty(m.ncells * 6 * problem.tables.nq ** 3, dtype=npdt)
+                self.k.dofmap_geometry(m.ncells, self.cverts, self.coords, self.G)
 
     def _run(self, cells, u, y):
-        from ..ops.native import ptr
-        if cells.size == 0:
-            return
-        t, pb = self.t, self.pb
-        self._fn(pb.lat.degree, pb.tables.nq, ptr(t["phi0"]), ptr(t["dphi1"]), ptr(t["wts"]),
-                 ptr(t["qpts"]), int(pb.tables.is_identity), ptr(cells), int(cells.size),
-                 ptr(self.cdofs), ptr(self.cverts), ptr(self.coords), ptr(self.G), ptr(self.flags),
-                 pb.kappa, ptr(self.kc), ptr(u), ptr(y))
+        if cells.size:
+            self.k.dofmap_apply(cells, self.cdofs, self.cverts, self.coords, self.G, self.flags,
+                                self.pb.kappa, self.kc, u, y)
 
     def apply(self, u: torch.Tensor, y: torch.Tensor) -> None:
         pb = self.pb

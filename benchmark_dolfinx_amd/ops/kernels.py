@@ -1,5 +1,6 @@
-"""Python front-end of the HIP kernels: torch tensors in, kernels on the
-current HIP stream, errors raised loudly (no silent fallback)."""
+"""Python front-ends of the native kernels, one per platform with the same
+method names: `HipKernels` (torch tensors in, kernels on the current HIP
+stream) and `HostKernels`.  Errors are raised loudly (no silent fallback)."""
 
 from __future__ import annotations
 
@@ -22,6 +23,11 @@ def _suf(dtype) -> str:
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+def _box(lo, hi):
+    """A cell box's corners as int64 arrays (kept alive by the caller)."""
+    return np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
 
 
 class HipError(RuntimeError):
@@ -107,16 +113,22 @@ def stencil27(A, lat) -> np.ndarray:
     return S
 
 
+def _lattice_vectors(shape, dtype, *vecs) -> None:
+    """`vecs` (None: absent) are `dtype` vectors of the lattice shape `shape`
+    (the kernels index them by lattice node)."""
+    for v in vecs:
+        if v is not None and (v.dtype != dtype or tuple(v.shape) != tuple(shape)):
+            raise TypeError(f"expected a {dtype} lattice vector of shape {tuple(shape)}, "
+                            f"got {v.dtype} {tuple(v.shape)}")
+
+
 def _stencil27_check(lat, dtype, S, *vecs) -> None:
     """S is the (27, nstore) stencil of lattice `lat` and `vecs` its lattice
-    vectors, all of `dtype` (the kernels index them by lattice node)."""
+    vectors, all of `dtype`."""
     if S.dtype != dtype or tuple(S.shape) != (27, lat.nstore) or not S.is_contiguous():
         raise TypeError(f"expected a contiguous {dtype} stencil of shape (27, {lat.nstore}), got "
                         f"{S.dtype} {tuple(S.shape)}")
-    for v in vecs:
-        if v is not None and (v.dtype != dtype or tuple(v.shape) != tuple(lat.shape)):
-            raise TypeError(f"expected a {dtype} lattice vector of shape {tuple(lat.shape)}, "
-                            f"got {v.dtype} {tuple(v.shape)}")
+    _lattice_vectors(lat.shape, dtype, *vecs)
 
 
 def _stencil27_assemble_check(lat, dtype, xv, kc, S) -> None:
@@ -181,33 +193,49 @@ class PmgTail:
         self.dev = torch.from_numpy(tab).to(device)
 
     def check(self, r, z) -> None:
-        for v in (r, z):
-            if v.dtype != self.dtype or tuple(v.shape) != self.shape:
-                raise TypeError(f"expected a {self.dtype} lattice vector of shape {self.shape}, "
-                                f"got {v.dtype} {tuple(v.shape)}")
+        _lattice_vectors(self.shape, self.dtype, r, z)
 
 
-class HipKernels:
-    """Bound kernel launchers for one problem (lattice + tables + dtype)."""
+class _Kernels:
+    """What the front-ends of the two native libraries share: one problem's
+    lattice, tables (None: a front-end for the table-free kernels only) and
+    dtype, bound to the library `lib`.  The kernels that platform-neutral
+    callers use have the same names and parameters on both
+    (tests/test_kernel_frontends.py)."""
 
-    def __init__(self, lat, tables, dtype):
-        self.lib = native.hip()
+    def __init__(self, lib, lat, tables, dtype):
+        self.lib = lib
         self.lat = lat
         self.latd = lat.as_int64()
-        self.t = TableSet(tables)
+        self.t = None if tables is None else TableSet(tables)
         self.dtype = dtype
         self.suf = _suf(dtype)
-        self.npart = self.lib.bdx_hip_partials_size()
         self.o = lat.owned_hi
         self.own = np.asarray(self.o, dtype=np.int64)
+        self.rows = (lat.L[1], lat.ld, *self.o)  # the owned-row walk's arguments
 
     def _f(self, name):
         return getattr(self.lib, f"{name}_{self.suf}")
 
+    def _rows(self, v64=(), v32=()):
+        """The row-walk arguments, after checking that the float64 and
+        float32 vectors are lattice vectors of those types (the kernels index
+        both with one offset)."""
+        _lattice_vectors(self.lat.shape, torch.float64, *v64)
+        _lattice_vectors(self.lat.shape, torch.float32, *v32)
+        return self.rows
+
+
+class HipKernels(_Kernels):
+    """Bound kernel launchers for one problem (lattice + tables + dtype)."""
+
+    def __init__(self, lat, tables, dtype):
+        super().__init__(native.hip(), lat, tables, dtype)
+        self.npart = self.lib.bdx_hip_partials_size()
+
     # --------------------------------------------------------------- operator
     def v1_apply(self, mode: int, G, xv, kappa: float, u, y, lo, hi, kc=None):
-        lo = np.asarray(lo, dtype=np.int64)
-        hi = np.asarray(hi, dtype=np.int64)
+        lo, hi = _box(lo, hi)
         t = self.t
         _check(self._f("bdx_v1_apply")(mode, ptr(self.latd), t.nq, ptr(t.phi0),
                                        ptr(t.dphi1), ptr(t.wts), ptr(t.qpts), t.identity,
@@ -217,8 +245,7 @@ class HipKernels:
     def diagonal(self, xv, kappa: float, kc, d, lo, hi):
         """d += matrix-free diag(A) of the cells [lo, hi) (lap_diag.h; Dirichlet
         dofs skipped, no atomics: eight colour launches in a fixed order)."""
-        lo = np.asarray(lo, dtype=np.int64)
-        hi = np.asarray(hi, dtype=np.int64)
+        lo, hi = _box(lo, hi)
         t = self.t
         _check(self._f("bdx_diag")(ptr(self.latd), t.nq, ptr(t.phi0), ptr(t.dphi1), ptr(t.wts),
                                    ptr(t.qpts), t.identity, ptr(xv), kappa, ptr(kc), ptr(d),
@@ -289,52 +316,40 @@ class HipKernels:
 
     # ------------------------------------------------------------------ BLAS
     def dot(self, a, b, partials, out, slot: int):
-        L = self.lat
-        _check(self._f("bdx_dot")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], ptr(a),
-                                  ptr(b), ptr(partials), ptr(out), slot, _stream()), "dot")
+        _check(self._f("bdx_dot")(*self.rows, ptr(a), ptr(b), ptr(partials), ptr(out), slot,
+                                  _stream()), "dot")
 
     def cg_update(self, x, r, p, y, scal, rn_slot, pap_slot, out_slot, partials):
-        L = self.lat
-        _check(self._f("bdx_cg_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
-                                        ptr(x), ptr(r), ptr(p), ptr(y), ptr(scal), rn_slot,
-                                        pap_slot, out_slot, ptr(partials), _stream()),
+        _check(self._f("bdx_cg_update")(*self.rows, ptr(x), ptr(r), ptr(p), ptr(y), ptr(scal),
+                                        rn_slot, pap_slot, out_slot, ptr(partials), _stream()),
                "cg_update")
 
     def p_update(self, p, r, scal, num, den):
-        L = self.lat
-        _check(self._f("bdx_p_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
-                                       ptr(p), ptr(r), ptr(scal), num, den, _stream()),
+        _check(self._f("bdx_p_update")(*self.rows, ptr(p), ptr(r), ptr(scal), num, den, _stream()),
                "p_update")
 
     def pcg_update(self, x, r, p, y, dinv, scal, rz_slot, pap_slot, out_slot, rr_slot, partials):
         """Jacobi PCG: alpha = s[rz] / s[pap]; x += alpha p; r -= alpha y;
         s[out] = sum dinv r^2 (the new r.z), s[rr] = sum r^2."""
-        L = self.lat
-        _check(self._f("bdx_pcg_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
-                                         ptr(x), ptr(r), ptr(p), ptr(y), ptr(dinv), ptr(scal),
-                                         rz_slot, pap_slot, out_slot, rr_slot, ptr(partials),
-                                         _stream()), "pcg_update")
+        _check(self._f("bdx_pcg_update")(*self.rows, ptr(x), ptr(r), ptr(p), ptr(y), ptr(dinv),
+                                         ptr(scal), rz_slot, pap_slot, out_slot, rr_slot,
+                                         ptr(partials), _stream()), "pcg_update")
 
     def pcg_p_update(self, p, r, dinv, scal, num, den):
         """p = (s[num] / s[den]) p + dinv . r."""
-        L = self.lat
-        _check(self._f("bdx_pcg_p_update")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2],
-                                           ptr(p), ptr(r), ptr(dinv), ptr(scal), num, den,
-                                           _stream()), "pcg_p_update")
+        _check(self._f("bdx_pcg_p_update")(*self.rows, ptr(p), ptr(r), ptr(dinv), ptr(scal), num,
+                                           den, _stream()), "pcg_p_update")
 
     def axpy(self, out, alpha: float, x, y):
-        L = self.lat
-        _check(self._f("bdx_axpy")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], ptr(out),
-                                   float(alpha), ptr(x), ptr(y), _stream()), "axpy")
+        _check(self._f("bdx_axpy")(*self.rows, ptr(out), float(alpha), ptr(x), ptr(y), _stream()),
+               "axpy")
 
     # --------------------------------------------------------- p-multigrid
     def cheb_step(self, first: bool, a: float, b: float, dinv, r, y, d, z):
         """d = a d + b dinv (r - y); z += d over the owned rows (first: d = z =
         b dinv r, y unused)."""
-        L = self.lat
-        _check(self._f("bdx_cheb_step")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], int(first),
-                                        float(a), float(b), ptr(dinv), ptr(r), ptr(y), ptr(d),
-                                        ptr(z), _stream()), "cheb_step")
+        _check(self._f("bdx_cheb_step")(*self.rows, int(first), float(a), float(b), ptr(dinv),
+                                        ptr(r), ptr(y), ptr(d), ptr(z), _stream()), "cheb_step")
 
     def prolong(self, latd_c, J, vc, vf):
         """vf = P vc from the coarse lattice `latd_c` to this (fine) lattice;
@@ -412,17 +427,6 @@ class HipKernels:
                                        ptr(r), ptr(z), _stream()), "pmg_tail")
 
     # ------------------------------------- FP64 CG around an FP32 cycle
-    def _rows(self, v64=(), v32=()):
-        """The row-walk arguments, after checking that the float64 and
-        float32 vectors are lattice vectors of those types (the kernels index
-        both with one offset)."""
-        for vs, dt in ((v64, torch.float64), (v32, torch.float32)):
-            for v in vs:
-                if v.dtype != dt or tuple(v.shape) != tuple(self.lat.shape):
-                    raise TypeError(f"expected a {dt} lattice vector of shape "
-                                    f"{tuple(self.lat.shape)}, got {v.dtype} {tuple(v.shape)}")
-        return self.lat.L[1], self.lat.ld, self.o[0], self.o[1], self.o[2]
-
     def demote(self, a, out):
         """out (float32) = a (float64) over the owned rows, round to nearest even."""
         _check(self.lib.bdx_demote_f64_f32(*self._rows((a,), (out,)), ptr(a), ptr(out), _stream()), "demote")
@@ -460,27 +464,93 @@ class HipKernels:
                                    ptr(y), int(acc), _stream()), "spmv")
 
 
-class HostKernels:
-    """The p-multigrid kernels of `HipKernels` on the host twins
-    (csrc/host/bdx_host_mg.cpp), so the CPU platform runs the same Python path."""
+class HostKernels(_Kernels):
+    """The front-end of the host library: `HipKernels`' twin on the CPU
+    platform (host tensors or numpy arrays in), and the host-only work of
+    either platform (interpolation of f, CSR assembly, the dofmap operator).
+    The operator kernels read the 1D tables in the vector dtype (`host_tables`);
+    without `tables` only the table-free multigrid kernels can be called."""
 
     def __init__(self, lat, dtype, tables=None):
-        self.lib = native.host()
-        self.lat = lat
-        self.latd = lat.as_int64()
-        self.t = None if tables is None else TableSet(tables)  # stencil27_assemble only
-        self.dtype = dtype
-        self.suf = _suf(dtype)
-        self.o = lat.owned_hi
-        self.own = np.asarray(self.o, dtype=np.int64)
+        super().__init__(native.host(), lat, tables, dtype)
+        npdt = np.float64 if dtype == torch.float64 else np.float32
+        self.host_tables = None if tables is None else {
+            k: np.ascontiguousarray(v, dtype=npdt) for k, v in dict(
+                phi0=tables.phi0, dphi1=tables.dphi1, wts=tables.qwts, qpts=tables.qpts,
+                nodes=tables.nodes, B=tables.B, Dd=tables.Dd).items()}
 
-    def _f(self, name):
-        return getattr(self.lib, f"{name}_{self.suf}")
+    # --------------------------------------------------------------- operator
+    def v1_apply(self, mode: int, G, xv, kappa: float, u, y, lo, hi, kc=None):
+        """Over the cells [lo, hi): y += A u with the stored geometry G (mode
+        0) or per-point geometry (1); y += M u (2)."""
+        lo, hi = _box(lo, hi)
+        t, h = self.t, self.host_tables
+        tabs = (ptr(self.latd), t.nq, ptr(h["phi0"]), ptr(h["dphi1"]), ptr(h["wts"]), ptr(h["qpts"]),
+                ptr(h["nodes"]), t.identity, ptr(xv))
+        if mode == 2:
+            self._f("bdx_cpu_mass")(*tabs, ptr(u), ptr(y), ptr(lo), ptr(hi))
+        else:
+            self._f("bdx_cpu_stiffness_g")(*tabs, ptr(G) if mode == 0 else None, kappa, ptr(kc),
+                                           ptr(u), ptr(y), ptr(lo), ptr(hi))
 
+    def diagonal(self, xv, kappa: float, kc, d, lo, hi):
+        lo, hi = _box(lo, hi)
+        t, h = self.t, self.host_tables
+        self._f("bdx_cpu_diag")(ptr(self.latd), t.nq, ptr(h["B"]), ptr(h["Dd"]), ptr(h["wts"]),
+                                ptr(h["qpts"]), ptr(xv), kappa, ptr(kc), ptr(d), ptr(lo), ptr(hi))
+
+    def geometry(self, xv, G):
+        h = self.host_tables
+        self._f("bdx_cpu_geometry")(ptr(self.latd), self.t.nq, ptr(h["wts"]), ptr(h["qpts"]),
+                                    ptr(xv), ptr(G))
+
+    def spmv(self, nrows, beg, end, cols, vals, x, y, acc=False):
+        self._f("bdx_cpu_spmv")(nrows, ptr(beg), ptr(end), ptr(cols), ptr(vals), ptr(x), ptr(y),
+                                int(acc))
+
+    def box_copy(self, mode: int, vec, lat, side, buf):
+        """Mode 0: buf = the entries of `side`'s boxes in table order; 1: those
+        entries = buf; 2: += buf."""
+        flat, buf = vec.view(-1), buf[: side.total]
+        if mode == 0:
+            torch.index_select(flat, 0, side.index, out=buf)
+        elif mode == 1:
+            flat.index_copy_(0, side.index, buf)
+        else:
+            flat.index_add_(0, side.index, buf)
+
+    # -------------------------------------------------------------- host only
+    def interp_f(self, xv, f):
+        """f = the source term at the physical dof nodes, all local points."""
+        self._f("bdx_cpu_interp_f")(ptr(self.latd), ptr(self.host_tables["nodes"]), ptr(xv), ptr(f))
+
+    def csr(self, xv, kappa: float, kc, row_ptr, cols=None, vals=None) -> int:
+        """The assembled local matrix: without `cols` and `vals` the row counts
+        into `row_ptr`, with them the matrix (`row_ptr` zeroed by the caller).
+        Returns the number of entries."""
+        t, h = self.t, self.host_tables
+        return self._f("bdx_cpu_csr")(ptr(self.latd), t.nq, ptr(h["B"]), ptr(h["Dd"]), ptr(h["wts"]),
+                                      ptr(h["qpts"]), ptr(xv), kappa, ptr(kc), ptr(row_ptr),
+                                      ptr(cols), ptr(vals), int(cols is None))
+
+    def dofmap_apply(self, cells, cdofs, cverts, coords, G, flags, kappa: float, kc, u, y):
+        """y += A u over `cells` of the unstructured data model (G None:
+        per-point geometry)."""
+        t, h = self.t, self.host_tables
+        self._f("bdx_cpu_dofmap")(self.lat.degree, t.nq, ptr(h["phi0"]), ptr(h["dphi1"]),
+                                  ptr(h["wts"]), ptr(h["qpts"]), t.identity, ptr(cells),
+                                  int(cells.size), ptr(cdofs), ptr(cverts), ptr(coords), ptr(G),
+                                  ptr(flags), kappa, ptr(kc), ptr(u), ptr(y))
+
+    def dofmap_geometry(self, ncells: int, cverts, coords, G):
+        h = self.host_tables
+        self._f("bdx_cpu_dofmap_geometry")(self.lat.degree, self.t.nq, ptr(h["wts"]), ptr(h["qpts"]),
+                                           ncells, ptr(cverts), ptr(coords), ptr(G))
+
+    # --------------------------------------------------------- p-multigrid
     def cheb_step(self, first: bool, a: float, b: float, dinv, r, y, d, z):
-        L = self.lat
-        self._f("bdx_cpu_cheb_step")(L.L[1], L.ld, self.o[0], self.o[1], self.o[2], int(first),
-                                     float(a), float(b), ptr(dinv), ptr(r), ptr(y), ptr(d), ptr(z))
+        self._f("bdx_cpu_cheb_step")(*self.rows, int(first), float(a), float(b), ptr(dinv), ptr(r),
+                                     ptr(y), ptr(d), ptr(z))
 
     def prolong(self, latd_c, J, vc, vf):
         if self._f("bdx_cpu_prolong")(ptr(latd_c), ptr(self.latd), ptr(J), ptr(vc), ptr(vf)):
@@ -539,30 +609,19 @@ class HostKernels:
         """`HipKernels.stencil27_assemble` on the host twin."""
         _stencil27_assemble_check(self.lat, self.dtype, xv, kc, S)
         t = self.t
-        if t is None:
-            raise ValueError("stencil27_assemble: these HostKernels were built without tables")
         if self._f("bdx_cpu_stencil27_assemble")(ptr(self.latd), t.nq, ptr(t.phi0), ptr(t.dphi1),
                                                  ptr(t.wts), ptr(t.qpts), ptr(xv), float(kappa),
                                                  ptr(kc), ptr(S)):
             raise ValueError("stencil27_assemble: not a degree-1 lattice with 2 or 3 quadrature "
                              "points per axis")
 
-    def _rows(self, a, da, out, do):
-        for v, dt in ((a, da), (out, do)):
-            if v.dtype != dt or tuple(v.shape) != tuple(self.lat.shape):
-                raise TypeError(f"expected a {dt} lattice vector of shape "
-                                f"{tuple(self.lat.shape)}, got {v.dtype} {tuple(v.shape)}")
-        return self.lat.L[1], self.lat.ld, self.o[0], self.o[1], self.o[2]
-
     def demote(self, a, out):
         """out (float32) = a (float64) over the owned rows, round to nearest even."""
-        self.lib.bdx_cpu_demote_f64_f32(*self._rows(a, torch.float64, out, torch.float32),
-                                        ptr(a), ptr(out))
+        self.lib.bdx_cpu_demote_f64_f32(*self._rows((a,), (out,)), ptr(a), ptr(out))
 
     def promote(self, a, out):
         """out (float64) = a (float32) over the owned rows (exact)."""
-        self.lib.bdx_cpu_promote_f32_f64(*self._rows(a, torch.float32, out, torch.float64),
-                                         ptr(a), ptr(out))
+        self.lib.bdx_cpu_promote_f32_f64(*self._rows((out,), (a,)), ptr(a), ptr(out))
 
     def axpy(self, out, alpha: float, x, y):
         o = self.o

@@ -43,7 +43,7 @@ class _Side:
             off += b.size
         self.table = torch.tensor(np.array(tab, dtype=np.int64).reshape(-1, 7),
                                   device=device)
-        # flat indices (CPU path and tests)
+        # flat indices (the host front-end's box_copy, and tests)
         idx = []
         L1, ld = lat.L[1], lat.ld
         for b in self.boxes:
@@ -56,11 +56,11 @@ class _Side:
 
 
 class HaloExchange:
-    def __init__(self, lat: LocalLattice, comm: Comm, dtype, device, kernels=None):
+    def __init__(self, lat: LocalLattice, comm: Comm, dtype, device, kernels):
         self.lat = lat
         self.comm = comm
         self.device = torch.device(device)
-        self.kernels = kernels  # ops.kernels.HipKernels on GPU, None on CPU
+        self.kernels = kernels  # the problem's front-end (ops.kernels): its box_copy
         self.owned_faces = _Side(lat.halo_send_boxes(), comm.size, lat, device)
         self.ghosts = _Side(lat.halo_recv_boxes(), comm.size, lat, device)
         n = max(self.owned_faces.total, self.ghosts.total, 1)
@@ -76,20 +76,12 @@ class HaloExchange:
     def _pack(self, x: torch.Tensor, side: _Side, buf: torch.Tensor):
         if side.total == 0:
             return
-        if self.kernels is not None:
-            self.kernels.box_copy(0, x, self.lat, side, buf)
-        else:
-            torch.index_select(x.view(-1), 0, side.index, out=buf[: side.total])
+        self.kernels.box_copy(0, x, self.lat, side, buf)
 
     def _unpack(self, x: torch.Tensor, side: _Side, buf: torch.Tensor, add: bool):
         if side.total == 0:
             return
-        if self.kernels is not None:
-            self.kernels.box_copy(2 if add else 1, x, self.lat, side, buf)
-        elif add:
-            x.view(-1).index_add_(0, side.index, buf[: side.total])
-        else:
-            x.view(-1).index_copy_(0, side.index, buf[: side.total])
+        self.kernels.box_copy(2 if add else 1, x, self.lat, side, buf)
 
     # ------------------------------------------------------------ exchanges
     def forward_begin(self, x: torch.Tensor):

@@ -126,10 +126,9 @@ class _Level:
 
     def __init__(self, pb: PoissonProblem):
         from ..driver import make_operator  # driver imports solvers.cg: import lazily
-        from ..ops.kernels import HostKernels
         self.pb = pb
         self.op = make_operator(pb, "auto", "auto")
-        self.k = pb.kernels if pb.kernels is not None else HostKernels(pb.lat, pb.dtype)
+        self.k = pb.kernels
         self.dinv = pb.jacobi_inverse()
         self.bc = pb.bc_mask()
         self.latd = pb.lat.as_int64()

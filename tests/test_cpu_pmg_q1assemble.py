@@ -48,7 +48,7 @@ from benchmark_dolfinx_amd.driver import make_operator
 from benchmark_dolfinx_amd.models import poisson
 from benchmark_dolfinx_amd.models.poisson import CSROperator, MatFreeLaplacianCPU, PoissonProblem
 from benchmark_dolfinx_amd.ops import native
-from benchmark_dolfinx_amd.ops.kernels import HostKernels, stencil27
+from benchmark_dolfinx_amd.ops.kernels import stencil27
 from benchmark_dolfinx_amd.ops.native import ptr
 from benchmark_dolfinx_amd.parallel.comm import Comm, run_threaded
 from benchmark_dolfinx_amd.solvers.cg import cg_solve
@@ -88,7 +88,7 @@ def _csr(pb) -> np.ndarray:
 def assemble(pb) -> torch.Tensor:
     """The new path through the launcher, into an S full of NaN."""
     S = torch.full((27, pb.lat.nstore), NAN, dtype=pb.dtype).to(pb.device)
-    k = pb.kernels if pb.kernels is not None else HostKernels(pb.lat, pb.dtype, pb.tables)
+    k = pb.kernels
     k.stencil27_assemble(pb.xv, pb.kappa, pb.kc, S)
     return S
 
@@ -302,11 +302,11 @@ def check_refusals(platform, dt):
         torch.cuda.synchronize()
     assert torch.isfinite(S.cpu()).all()
     # the launchers raise
-    k2 = pb2.kernels if pb2.kernels is not None else HostKernels(pb2.lat, dt, pb2.tables)
+    k2 = pb2.kernels
     S2 = torch.zeros((27, pb2.lat.nstore), dtype=dt).to(pb2.device)
     with pytest.raises((ValueError, RuntimeError)):
         k2.stencil27_assemble(pb2.xv, pb2.kappa, pb2.kc, S2)
-    k = pb.kernels if pb.kernels is not None else HostKernels(pb.lat, dt, pb.tables)
+    k = pb.kernels
     with pytest.raises(TypeError):
         k.stencil27_assemble(pb.xv, pb.kappa, pb.kc, S[:26])
     with pytest.raises(TypeError):

@@ -33,7 +33,7 @@ import torch
 from benchmark_dolfinx_amd.driver import make_operator
 from benchmark_dolfinx_amd.models.poisson import CSROperator, MatFreeLaplacianCPU, PoissonProblem
 from benchmark_dolfinx_amd.ops import native
-from benchmark_dolfinx_amd.ops.kernels import HostKernels, stencil27
+from benchmark_dolfinx_amd.ops.kernels import stencil27
 from benchmark_dolfinx_amd.ops.native import ptr
 from benchmark_dolfinx_amd.parallel.comm import Comm, run_threaded
 from benchmark_dolfinx_amd.solvers.cg import cg_solve
@@ -62,7 +62,7 @@ def _pb(nc, P=1, dt=torch.float64, platform="cpu", comm=None, pert=0.2, coef="ra
 
 
 def _kern(pb):
-    return pb.kernels if pb.kernels is not None else HostKernels(pb.lat, pb.dtype)
+    return pb.kernels
 
 
 def _stencil(pb):

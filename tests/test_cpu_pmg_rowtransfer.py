@@ -26,7 +26,6 @@ import torch
 from benchmark_dolfinx_amd.fem.mesh import make_local_lattice
 from benchmark_dolfinx_amd.fem.quadrature import gll, lagrange_tables
 from benchmark_dolfinx_amd.models.poisson import MatFreeLaplacianCPU
-from benchmark_dolfinx_amd.ops.kernels import HostKernels
 from benchmark_dolfinx_amd.parallel.comm import Comm, run_threaded
 from benchmark_dolfinx_amd.solvers.cg import cg_solve
 from benchmark_dolfinx_amd.solvers.pmg import PMultigrid, chebyshev_coefficients
@@ -52,7 +51,7 @@ def _table(Pf, Pc):
 
 
 def _kern(pb):
-    return pb.kernels if pb.kernels is not None else HostKernels(pb.lat, pb.dtype)
+    return pb.kernels
 
 
 def _pair(nc, Pf, Pc, dt, platform="cpu", comm=None):
