@@ -23,6 +23,44 @@ constexpr int kMaxNq = 9;
 constexpr int kFusedTabMax = 2 * 9 * 12 + 9 * 8 + 8 * 12;
 // kGeomStored / kGeomOTF: bdx_rt_setup.h (through bdx_hip_api.h)
 
+// Layout of the tile-interface buffers of the fused operators (nty x ntz tiles
+// of sy x sz nodes): a tile's contributions to nodes its upper neighbours own,
+//   YB [Lx][nty-1][Lz]     rows y = (ty+1) sy,  ty = 0 .. nty-2
+//   ZB [Lx][ntz-1][Ly]     columns z = (tz+1) sz (a tile's face contiguous)
+//   CB [Lx][nty-1][ntz-1]  their crossings
+// written by the operator kernels plane by plane (the *bps strides), folded
+// into y by the CG update pass (cg_update.hip) or the finalize pass
+// (lap_fused.h).  The index arithmetic runs in the arguments' types (32-bit x
+// and tile numbers in the update kernels, int64_t in the finalize kernels).
+struct IfaceLayout {
+  int64_t Lx, Ly, Lz;
+  int nty, ntz;
+
+  BDX_HD static IfaceLayout of(const BdxLattice& lat, int nty, int ntz) {
+    return IfaceLayout{lat.L[0], lat.L[1], lat.L[2], nty, ntz};
+  }
+  // element of plane x: YB row ty at z, ZB column tz at y, CB crossing (ty, tz)
+  template <typename X, typename I, typename K>
+  BDX_HD auto yb(X x, I ty, K z) const {
+    return (x * (nty - 1) + ty) * Lz + z;
+  }
+  template <typename X, typename I, typename J>
+  BDX_HD auto zb(X x, I tz, J y) const {
+    return (x * (ntz - 1) + tz) * Ly + y;
+  }
+  template <typename X, typename I>
+  BDX_HD auto cb(X x, I ty, I tz) const {
+    return (x * (nty - 1) + ty) * (ntz - 1) + tz;
+  }
+  // elements per x-plane, and in all Lx planes
+  BDX_HD int64_t ybps() const { return static_cast<int64_t>(nty - 1) * Lz; }
+  BDX_HD int64_t zbps() const { return Ly * static_cast<int64_t>(ntz - 1); }
+  BDX_HD int64_t cbps() const { return static_cast<int64_t>(nty - 1) * (ntz - 1); }
+  BDX_HD int64_t yb_size() const { return Lx * (nty - 1) * Lz; }
+  BDX_HD int64_t zb_size() const { return Lx * Ly * (ntz - 1); }
+  BDX_HD int64_t cb_size() const { return Lx * (nty - 1) * (ntz - 1); }
+};
+
 // FP64 MFMA operand / accumulator vectors (v_mfma_f64_16x16x4f64: 4 results per lane)
 typedef double bdx_f64x4 __attribute__((ext_vector_type(4)));
 typedef double bdx_f64x2 __attribute__((ext_vector_type(2)));

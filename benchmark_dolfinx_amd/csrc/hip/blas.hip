@@ -254,7 +254,7 @@ int box_copy_vi(int mode, T* vec, VecIdx vi, const int64_t* boxes, int nboxes, i
 
 extern "C" {
 
-int bdx_hip_partials_size() { return 65536; }  // >= kPartialsCap (fused_common.hip)
+int bdx_hip_partials_size() { return 65536; }  // >= kPartialsCap (cg_update.hip)
 
 // Fixed-order reduction of n per-block partials into out[slot].
 int bdx_reduce_partials(const double* partials, int n, double* out, int slot,

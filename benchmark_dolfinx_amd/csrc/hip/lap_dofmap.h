@@ -930,7 +930,7 @@ constexpr int kDofUpdU = 4;
 // 3.07 -> 2.74, +1.5 % / +2-4 % GDoF/s same box (profiles/r4_update_pass_ab.txt).
 // Round 5: U vectors per thread per pass of the grid-stride loop, every load
 // of a pass issued before any arithmetic (the tiled update pass's form,
-// fused_common.hip): with one vector per thread and pass the loop kept a
+// cg_update.hip): with one vector per thread and pass the loop kept a
 // single 16-byte r / y pair in flight per thread and ran 1.56 ms on one box
 // and 2.17 ms on another at Q3 (profiles/r5_dofmap_update.md).
 template <typename T, int U, bool ZERO>

@@ -663,18 +663,20 @@ __global__ void __launch_bounds__((FusedShape<T, ND, NQ, TY, TZ>::threads), Fuse
 
 // Fold the interface partials into y (all local dofs incl. ghost planes).
 // Index space: [YB rows: Lx * (nty-1) * Lz] ++ [ZB columns not on a YB row:
-// Lx * Ly * (ntz-1)].  The two dof sets are disjoint, so no races.
+// Lx * Ly * (ntz-1)], each in its buffer's own element order (IfaceLayout: t is
+// F.yb(x, tym1, z), s is F.zb(x, tzm1, yy)).  The two dof sets are disjoint,
+// so no races.
 // ghost_only: fold only dofs on this rank's ghost planes (the CG path folds
-// the owned dofs inside the CG update, fused_common.hip; the ghost planes must
+// the owned dofs inside the CG update, cg_update.hip; the ghost planes must
 // be complete before the reverse halo exchange packs them).
 template <typename T>
 __global__ void __launch_bounds__(256)
     fused_finalize_kernel(BdxLattice lat, T* __restrict__ y, const T* __restrict__ yb,
                           const T* __restrict__ zb, const T* __restrict__ cb, int nty,
                           int ntz, int sy, int sz, int ghost_only) {
-  const int64_t Lx = lat.L[0], Ly = lat.L[1], Lz = lat.L[2];
-  const int64_t n1 = Lx * (nty - 1) * Lz;
-  const int64_t n2 = Lx * Ly * (ntz - 1);
+  const IfaceLayout F = IfaceLayout::of(lat, nty, ntz);
+  const int64_t Ly = F.Ly, Lz = F.Lz;
+  const int64_t n1 = F.yb_size(), n2 = F.zb_size();
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < n1 + n2;
        t += static_cast<int64_t>(gridDim.x) * blockDim.x) {
     if (t < n1) {
@@ -686,8 +688,8 @@ __global__ void __launch_bounds__(256)
       T add = yb[t];
       const int64_t tzz = z / sz;
       if (z % sz == 0 && tzz >= 1 && tzz < ntz) {
-        add += zb[(x * (ntz - 1) + (tzz - 1)) * Ly + yy];
-        add += cb[(x * (nty - 1) + tym1) * (ntz - 1) + (tzz - 1)];
+        add += zb[F.zb(x, tzz - 1, yy)];
+        add += cb[F.cb(x, tym1, tzz - 1)];
       }
       y[lat.sidx(x, yy, z)] += add;
     } else {
@@ -717,10 +719,11 @@ __global__ void __launch_bounds__(256)
     fused_finalize_ghost_kernel(BdxLattice lat, T* __restrict__ y, const T* __restrict__ yb,
                                 const T* __restrict__ zb, const T* __restrict__ cb, int nty,
                                 int ntz, int sy, int sz) {
-  const int64_t Lx = lat.L[0], Ly = lat.L[1], Lz = lat.L[2];
+  const IfaceLayout F = IfaceLayout::of(lat, nty, ntz);
+  const int64_t Lx = F.Lx, Ly = F.Ly, Lz = F.Lz;
   const bool gx = lat.gh[0], gy = lat.gh[1], gz = lat.gh[2];
   const int64_t xB = gx ? Lx - 1 : Lx;  // x range of parts B, C
-  const int64_t nA1 = gx ? (nty - 1) * Lz : 0, nA2 = gx ? Ly * (ntz - 1) : 0;
+  const int64_t nA1 = gx ? F.ybps() : 0, nA2 = gx ? F.zbps() : 0;
   const int64_t nB = gy ? xB * (ntz - 1) : 0;
   const int64_t nC = gz ? xB * (nty - 1) : 0;
   const int64_t ntot = nA1 + nA2 + nB + nC;
@@ -729,11 +732,11 @@ __global__ void __launch_bounds__(256)
     if (t < nA1) {  // YB row entry on the x ghost plane
       const int64_t x = Lx - 1, z = t % Lz, tym1 = t / Lz;
       const int64_t yy = (tym1 + 1) * sy;
-      T add = yb[(x * (nty - 1) + tym1) * Lz + z];
+      T add = yb[F.yb(x, tym1, z)];
       const int64_t tzz = z / sz;
       if (z % sz == 0 && tzz >= 1 && tzz < ntz) {
-        add += zb[(x * (ntz - 1) + (tzz - 1)) * Ly + yy];
-        add += cb[(x * (nty - 1) + tym1) * (ntz - 1) + (tzz - 1)];
+        add += zb[F.zb(x, tzz - 1, yy)];
+        add += cb[F.cb(x, tym1, tzz - 1)];
       }
       y[lat.sidx(x, yy, z)] += add;
     } else if (t < nA1 + nA2) {  // ZB column entry on the x ghost plane
@@ -741,15 +744,15 @@ __global__ void __launch_bounds__(256)
       const int64_t yy = s % Ly, tzm1 = s / Ly;
       const int64_t tyy = yy / sy;
       if (yy % sy == 0 && tyy >= 1 && tyy < nty) continue;  // on a YB row: done above
-      y[lat.sidx(x, yy, (tzm1 + 1) * sz)] += zb[(x * (ntz - 1) + tzm1) * Ly + yy];
+      y[lat.sidx(x, yy, (tzm1 + 1) * sz)] += zb[F.zb(x, tzm1, yy)];
     } else if (t < nA1 + nA2 + nB) {  // ZB column entry on the y ghost plane
       const int64_t s = t - nA1 - nA2, yy = Ly - 1;
       const int64_t tzm1 = s % (ntz - 1), x = s / (ntz - 1);
-      y[lat.sidx(x, yy, (tzm1 + 1) * sz)] += zb[(x * (ntz - 1) + tzm1) * Ly + yy];
+      y[lat.sidx(x, yy, (tzm1 + 1) * sz)] += zb[F.zb(x, tzm1, yy)];
     } else {  // YB row entry on the z ghost plane
       const int64_t s = t - nA1 - nA2 - nB, z = Lz - 1;
       const int64_t tym1 = s % (nty - 1), x = s / (nty - 1);
-      y[lat.sidx(x, (tym1 + 1) * sy, z)] += yb[(x * (nty - 1) + tym1) * Lz + z];
+      y[lat.sidx(x, (tym1 + 1) * sy, z)] += yb[F.yb(x, tym1, z)];
     }
   }
 }

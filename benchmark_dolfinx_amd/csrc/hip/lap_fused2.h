@@ -18,6 +18,7 @@
 //
 // Interface partials (YB/ZB/CB) and the finalize pass are those of v1.
 #pragma once
+#include <algorithm>
 #include "lap_fused.h"
 
 // The LDS-fed contraction loops stay rolled (BDX_PRAGMA_UNROLL(1)): keeps the
@@ -819,13 +820,11 @@ inline int make_fused2_args(Fused2Args<T>& a, const int64_t* latd, int nty, int 
     if (L.size() >= (int64_t(1) << 31) || L.tsz <= 0) return static_cast<int>(hipErrorInvalidValue);
     a.ps = L.tsy * L.tsz;
   }
-  a.ybps = static_cast<int64_t>(nty - 1) * L.L[2];
-  a.zbps = L.L[1] * static_cast<int64_t>(ntz - 1);
-  a.cbps = static_cast<int64_t>(nty - 1) * (ntz - 1);
-  {
-    const int64_t y_ = L.L[0] * a.ybps, z_ = L.L[0] * a.zbps, c_ = L.L[0] * a.cbps;
-    a.ibsize = y_ > z_ ? (y_ > c_ ? y_ : c_) : (z_ > c_ ? z_ : c_);
-  }
+  const IfaceLayout F = IfaceLayout::of(L, nty, ntz);
+  a.ybps = F.ybps();
+  a.zbps = F.zbps();
+  a.cbps = F.cbps();
+  a.ibsize = std::max({F.yb_size(), F.zb_size(), F.cb_size()});
   a.vps = (L.n[1] + 1) * (L.n[2] + 1) * 3;
   a.ncx = static_cast<int>(L.n[0]);
   a.n1 = static_cast<int>(L.n[1]);

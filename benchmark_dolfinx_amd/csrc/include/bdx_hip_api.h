@@ -91,7 +91,7 @@ BDX_TWINS(int, bdx_layout_convert, BDX_P_LAYOUT_CONVERT)
   const double* scal, int num1, int den1, int num2, int den2, int p2mask, hipStream_t st)
 BDX_TWINS(int, bdx_flush_export, BDX_P_FLUSH_EXPORT)
 
-// ---------------------------------------------------------- fused_common.hip
+// ------------------------------------------- cg_update.hip, fused_common.hip
 // CG update of the fused2..5 paths, lattice layout: alpha = s[rn_slot] /
 // s[pap_slot]; r -= alpha (y + the tile-interface partials yb / zb / cb, folded
 // on the fly); r.r over the owned nodes -> scal[out_slot].  x is not touched

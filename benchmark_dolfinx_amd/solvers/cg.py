@@ -26,7 +26,7 @@ When the operator provides `cg_start` / `cg_iterate` (the fused structured
 kernel, models/fused.py) the device loop delegates to it.  The preconditioned
 solve does so only on request (`loop="fused"`): the fused kernels then run
 with u = z = dinv . r, r.z in the r.r slots, and an update pass that also
-stores z (csrc/hip/fused_common.hip).
+stores z (csrc/hip/cg_update.hip).
 """
 
 from __future__ import annotations

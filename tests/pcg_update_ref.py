@@ -1,5 +1,5 @@
 """Plain reference of the Jacobi-preconditioned update pass of the fused CG
-loop (csrc/hip/fused_common.hip, bdx_pcg_update_iface_* / bdx_pcg_update_tiled_*),
+loop (csrc/hip/cg_update.hip, bdx_pcg_update_iface_* / bdx_pcg_update_tiled_*),
 on top of tests/vector_ref.py:
 
     r_new = r - alpha (y + interface terms)     on the owned nodes

@@ -1,5 +1,5 @@
 """The Jacobi-preconditioned update pass of the fused CG loop
-(bdx_pcg_update_iface_*, bdx_pcg_update_tiled_*; csrc/hip/fused_common.hip),
+(bdx_pcg_update_iface_*, bdx_pcg_update_tiled_*; csrc/hip/cg_update.hip),
 driven directly through its C entry points with hand-built lattice descriptors.
 
 Per case:
@@ -31,10 +31,12 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_harness as kh
 import pcg_update_ref as pr
 import vector_ref as vr
-from benchmark_dolfinx_amd.ops import native
 from benchmark_dolfinx_amd.ops.native import ptr
+from kernel_harness import (assert_same_bits, dev, fn, geom, host, iface_flat, lib,
+                            new_partials, store, stream)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +47,7 @@ TYPES = {"f64": (np.float64, torch.float64), "f32": (np.float32, torch.float32)}
 RN, PAP, OUT, RR = 0, 2, 1, 5         # scalar slots: r.z (old), p.Ap, r.z (new), r.r
 SCAL = {RN: 0.8125, PAP: 1.37}
 PATHS = ["flat", "tiled_pre", "tiled_plain"]
+scalars = functools.partial(kh.scalars, SCAL)
 
 # P, kernel tile (cells), local cells, ghost planes: the smallest shapes with
 # both interface kinds, ghost planes, a tile-corner buffer, a non-ROW FP32
@@ -89,57 +92,6 @@ def test_refused_combinations_are_what_the_shape_table_predicts():
 
 
 # ------------------------------------------------------------------ helpers
-def lib():
-    return native.hip()
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def fn(name, suf):
-    return getattr(lib(), f"{name}_{suf}")
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True, order="C")).to("cuda")
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64 if a.dtype.itemsize == 8 else np.int32)
-
-
-def assert_same_bits(a, b, what):
-    diff = np.flatnonzero(bits(a) != bits(b))
-    assert diff.size == 0, f"{what}: {diff.size} elements differ, first at {diff[:8]}"
-
-
-def store(g, tiled, dense, T, fill=NAN):
-    s = np.full(g.size(tiled), fill, dtype=T)
-    s[g.map(tiled)] = dense
-    return s
-
-
-def iface_flat(a, T):
-    return a.ravel() if a.size else np.full(1, NAN, dtype=T)
-
-
-def scalars():
-    s = np.full(8, NAN)
-    for k, v in SCAL.items():
-        s[k] = v
-    return s
-
-
-def new_partials():
-    return torch.full((lib().bdx_hip_partials_size(),), NAN, dtype=torch.float64, device="cuda")
-
-
 def check_sum(got, terms, what):
     """got against math.fsum(terms) within n eps sum|terms|."""
     terms = np.asarray(terms, dtype=np.float64).ravel()
@@ -175,11 +127,6 @@ def call_pcg(g, suf, tiled, d_r, d_y, d_ifc, d_scal, parts, d_dinv, d_z):
         ptr(desc), ptr(own64), ptr(d_r), ptr(d_y), ptr(d_ifc[0]), ptr(d_ifc[1]), ptr(d_ifc[2]),
         g.nty, g.ntz, g.sy, g.sz, ptr(d_scal), RN, PAP, OUT, ptr(parts[0]), ptr(d_dinv), ptr(d_z),
         RR, ptr(parts[1]), stream())
-
-
-@functools.lru_cache(maxsize=None)
-def geom(P, tile, n, gh=(0, 0, 0)):
-    return vr.Geom(P, tile, n, gh)
 
 
 @functools.lru_cache(maxsize=4)

@@ -38,9 +38,11 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_harness as kh
 import vector_ref as vr
-from benchmark_dolfinx_amd.ops import native
 from benchmark_dolfinx_amd.ops.native import ptr
+from kernel_harness import (assert_same_bits, dev, fn, geom, host, iface_flat, lib,
+                            new_partials, store, stream)
 from benchmark_dolfinx_amd.parallel.halo import _Side
 
 pytestmark = pytest.mark.gpu
@@ -50,7 +52,8 @@ NAN = float("nan")
 TYPES = {"f64": (np.float64, torch.float64), "f32": (np.float32, torch.float32)}
 RN, PAP, OUT, XS = 0, 2, 5, 3        # scalar slots used by the calls
 SCAL = {RN: 0.8125, PAP: 1.37, XS: -0.4375, 6: 2.25}
-TWO_STAGE = 1024                      # 4 * kStage1 (fused_common.hip)
+TWO_STAGE = 1024                      # 4 * kStage1 (cg_update.hip)
+scalars = functools.partial(kh.scalars, SCAL)
 
 # P, kernel tile (cells), local cells, ghost planes
 A_SHAPES = {
@@ -77,37 +80,6 @@ B_SHAPES = {
 
 
 # ------------------------------------------------------------------ helpers
-def lib():
-    return native.hip()
-
-
-def stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def fn(name, suf):
-    return getattr(lib(), f"{name}_{suf}")
-
-
-def dev(a):
-    return torch.from_numpy(np.array(a, copy=True, order="C")).to("cuda")
-
-
-def host(t):
-    torch.cuda.synchronize()
-    return t.cpu().numpy()
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int64 if a.dtype.itemsize == 8 else np.int32)
-
-
-def assert_same_bits(a, b, what):
-    ba, bb = bits(a), bits(b)
-    diff = np.flatnonzero(ba != bb)
-    assert diff.size == 0, f"{what}: {diff.size} elements changed, first at {diff[:8]}"
-
-
 def assert_close(out, ref, tol, where, what):
     """|out - ref| <= tol on `where` (NaN fails)."""
     assert np.isfinite(out[where]).all(), f"{what}: non-finite output"
@@ -124,29 +96,6 @@ def rand(rng, shape, T):
     return rng.standard_normal(shape).astype(T)
 
 
-def store(g, tiled, dense, T, fill=NAN):
-    """Storage array of a dense node array (padding = fill)."""
-    s = np.full(g.size(tiled), fill, dtype=T)
-    s[g.map(tiled)] = dense
-    return s
-
-
-def iface_flat(a, T):
-    """An interface buffer as production allocates it: max(1, size) elements."""
-    return a.ravel() if a.size else np.full(1, NAN, dtype=T)
-
-
-def scalars():
-    s = np.full(8, NAN)
-    for k, v in SCAL.items():
-        s[k] = v
-    return s
-
-
-def new_partials():
-    return torch.full((lib().bdx_hip_partials_size(),), NAN, dtype=torch.float64, device="cuda")
-
-
 def check_sum(got, terms, chain, mag=None, extra=0.0, what="sum"):
     """got against fsum(terms) within (chain + 3) 2^-53 of sum|terms| (+ extra)."""
     ref = vr.sum_hi(terms)
@@ -155,11 +104,6 @@ def check_sum(got, terms, chain, mag=None, extra=0.0, what="sum"):
     bound = (chain + 3) * vr.U53 * scale + extra
     assert abs(got - ref) <= bound, (f"{what}: got {got!r}, reference {ref!r}, "
                                      f"difference {abs(got - ref):.3e} > bound {bound:.3e}")
-
-
-@functools.lru_cache(maxsize=None)
-def geom(P, tile, n, gh=(0, 0, 0), lower=False):
-    return vr.Geom(P, tile, n, gh, lower)
 
 
 # ------------------------------------------------ A: interface-fold update

@@ -1,5 +1,5 @@
 """Plain references of the CG runtime's vector kernels (csrc/hip/blas.hip,
-csrc/hip/fused_common.hip, the finalize kernels of csrc/hip/lap_fused.h).
+csrc/hip/cg_update.hip, the finalize kernels of csrc/hip/lap_fused.h).
 
 Everything here works on dense (L0, L1, L2) node arrays and on explicit
 storage maps; nothing is shared with the kernels.  The array functions use
