@@ -262,7 +262,9 @@ struct ThreadGroupState {
   }
 };
 std::mutex g_groups_m;
-std::map<int64_t, std::shared_ptr<ThreadGroupState>> g_groups;
+// found by group id while a runtime of the group holds it (runtime.hip:
+// init_common joins, bdx_rt_release_group drops the expired entry)
+std::map<int64_t, std::weak_ptr<ThreadGroupState>> g_groups;
 
 // The exchange is stream-ordered, as RCCL's: the host only swaps buffer
 // pointers and event handles at two barriers and never waits for the device,

@@ -297,9 +297,13 @@ struct LoopBase {
       auto t = std::make_unique<ThreadTransport>();
       {
         std::lock_guard<std::mutex> lk(g_groups_m);
-        auto& g = g_groups[h.group_id];
+        // joined while any rank's runtime still holds it: a rank that
+        // replaces its runtime (a new DeviceCG on the same operator) before
+        // its peers have closed theirs has to end up on the same state
+        std::shared_ptr<ThreadGroupState> g = g_groups[h.group_id].lock();
         if (!g) {
           g = std::make_shared<ThreadGroupState>();
+          g_groups[h.group_id] = g;
           g->size = n;
           g->sbuf.assign(n, nullptr);
           g->soff.assign(n, nullptr);
@@ -1368,9 +1372,13 @@ int bdx_rt_state(void* h, long* it, int* graphs) {
 
 void bdx_rt_destroy(void* h) { delete static_cast<LoopBase*>(h); }
 
+// Called by every rank after it destroyed its runtime: the entry goes with
+// the last runtime of the group (the runtimes own the state, the map only
+// finds it).
 void bdx_rt_release_group(int64_t group_id) {
   std::lock_guard<std::mutex> lk(g_groups_m);
-  g_groups.erase(group_id);
+  auto it = g_groups.find(group_id);
+  if (it != g_groups.end() && it->second.expired()) g_groups.erase(it);
 }
 
 }  // extern "C"

@@ -204,6 +204,34 @@ def test_devicecg_solves_twice_with_different_iterates():
     op.close()
 
 
+def _two_cg_job(comm, nc, P, nreps):
+    pb = PoissonProblem(comm, nc, P, 1, False, torch.float64, "gpu", partition="yz")
+    u = pb.assemble_rhs()
+    op = FusedLaplacianGPU(pb, "otf", 3)
+    norms = []
+    for _ in range(2):
+        x = pb.new_vector()
+        cg = DeviceCG(pb)           # a new loop state: the operator replaces its runtime
+        cg.solve(op, x, u, nreps)
+        cg.wait()
+        norms.append(pb.norm(x))
+        assert op._rt is not None and op._rt.cg is cg and op._rt.transport == "thread"
+    op.close()
+    return norms
+
+
+def test_second_devicecg_on_a_threaded_operator():
+    """A second DeviceCG on the same operator makes every rank close its
+    runtime and build a new one, with no barrier in between: a rank that has
+    already rebuilt must still share the thread transport's group state with
+    the peers that close theirs afterwards (the group table used to drop the
+    entry on every close, which left the ranks on two states and their
+    barriers waiting for each other)."""
+    for ranks in (2, 4):
+        for a, b in run_threaded(ranks, _two_cg_job, (3, 4, 5), 3, 4):
+            assert a > 0 and abs(a - b) <= 1e-11 * a, (a, b)
+
+
 def test_phase_profile_single_and_threaded():
     def job(comm):
         pb = PoissonProblem(comm, (4, 16, 18), 3, 1, False, torch.float64, "gpu")
